@@ -18,15 +18,23 @@ Multi-GPU (torchrun, one process per GPU): contiguous shards, no data-path colle
 proofs of the whole job, split over the ranks (strong scaling, configs[3]).  value = all
 ranks' proofs / max-over-ranks time.
 
-Every line, at every N, carries a "c4" object: configs[3] at this world size -- 2^26 proofs split
-over the ranks, per-rank RLC partial keyed by the global index, all-gather of the 32-byte
-partials (RCCL over xGMI at N > 1), combine, barrier-timed and max over ranks; the valid set
-must combine to the identity, and a forged variant (s + 1 in two ranks' shards) must give every
-rank exactly its forged statuses and a non-identity total.  Fewer visible GPUs than ranks is
-refused before the process group is set up.
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it
+sets up, warms up, times the K steps, writes the outputs of the last timed step if
+--dump-outputs DIR is given (DIR/<name>.npy, float32; the inputs are the same from run to run, so
+two builds can be compared output for output; since valid proofs give all-zero statuses, the
+same call is made once more, untimed, on the inputs with 64 fixed rows spoiled: probe_*.npy),
+and prints the line.  Everything below is
+measured only with --full, and the options that select among it apply only there.
 
-At N = 1 the same run also measures (reported beside value, never as value): the RLC batch
-check of the same proofs with per-kernel roofline fractions (configs[2]), the 2^24-proof
+With --full every line, at every N, carries a "c4" object: configs[3] at this world size -- 2^26
+proofs split over the ranks, per-rank RLC partial keyed by the global index, all-gather of the
+32-byte partials (RCCL over xGMI at N > 1), combine, barrier-timed and max over ranks; the valid
+set must combine to the identity, and a forged variant (s + 1 in two ranks' shards) must give
+every rank exactly its forged statuses and a non-identity total.  Fewer visible GPUs than ranks
+is refused before the process group is set up.
+
+With --full at N = 1 the same run also measures (reported beside value, never as value): the RLC
+batch check of the same proofs with per-kernel roofline fractions (configs[2]), the 2^24-proof
 batch with 0.1 % forged proofs through the batch check + fallback (configs[4]), the prover
 (proof generation, published ~144 us/proof, lib.rs:55), the host-buffer entry point (PCIe
 included), the per-call latency of BatchVerifier-sized batches (n = 1 .. 1000, both entry
@@ -615,6 +623,48 @@ def c4_run(gpu, torch, dist, dev, stream, world, rank, n_total, steps, warmup, b
     return out
 
 
+PROBE_ROWS = 64
+
+
+def probe_inputs(torch, t, n):
+    """The benchmark's inputs with up to PROBE_ROWS fixed rows (seeded) spoiled, a quarter each:
+    s + 1, y1 of the row seven further on, an r1 that decodes to no point (01 00 .. 00), s = 0.
+    Returns (inputs, rows): device tensors -- y1, r1, s are copies, y2, r2 shared -- and the
+    sorted row indices.  For --dump-outputs only; the timed steps never see it."""
+    import numpy as np
+    rows = np.unique(np.random.default_rng(4242).integers(0, n, size=PROBE_ROWS))
+    dev = t["s"].device
+    p = dict(t, y1=t["y1"].clone(), r1=t["r1"].clone(), s=t["s"].clone())
+    swap, bad, zero = (torch.from_numpy(rows[k::4].astype(np.int64)).to(dev) for k in (1, 2, 3))
+    _bump_s(torch, p, rows[0::4])
+    p["y1"].index_copy_(0, swap, t["y1"].index_select(0, (swap + 7) % n))
+    undecodable = torch.zeros((len(bad), 32), dtype=torch.uint8, device=dev)
+    undecodable[:, 0] = 1
+    p["r1"].index_copy_(0, bad, undecodable)
+    p["s"].index_fill_(0, zero, 0)
+    return p, rows
+
+
+DUMP_MAX_ROWS = 1 << 22  # 16 MiB of float32 per array: far inside the 64 MB a dump may take
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """Write what the timed path returned in its last step as <dirname>/<name>.npy (float32, row
+    indices float64; at N > 1 every rank writes <name>_rank<r>.npy).  An array of more than DUMP_MAX_ROWS rows is cut
+    to a fixed sample of its rows (seeded, sorted), whose indices go to <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.shape and a.shape[0] > DUMP_MAX_ROWS:
+            rows = np.sort(np.random.default_rng(20240).choice(a.shape[0], size=DUMP_MAX_ROWS, replace=False))
+            np.save(os.path.join(dirname, name + "_rows" + tag + ".npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + tag + ".npy"),
+                a.astype(np.float64 if a.dtype == np.int64 else np.float32))
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -649,6 +699,14 @@ def main():
     ap.add_argument("--n", type=int, default=1 << 20, help="proofs per GPU (weak scaling)")
     ap.add_argument("--n-total", type=int, default=0,
                     help="proofs of the whole job, split over the ranks (strong scaling; configs[3] = 67108864)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: configs[3] (c4), the CPU baseline and the "
+                         "N=1 extras (RLC check, C5, prover, host path, small-batch and custom-pair tables); the "
+                         "options below that select among these apply only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (the statuses; in rlc mode also "
+                         "the 32-byte partial and the verdict) as DIR/<name>.npy, float32, and beside them the "
+                         "same call's outputs for the inputs with 64 fixed rows spoiled (probe_*.npy, untimed)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (rank 0, N=1)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU baseline threads (0: the usable cores, min(affinity CPUs, cgroup quota))")
@@ -681,6 +739,10 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank uses cuda:0 (with --backend gloo); not a measurement")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline's steps only
+        args.extras = args.rlc_extra = args.host_e2e = args.small_batch = 0
+        args.c4_n = 0
+        args.no_cpu_baseline = True
     extra = lambda v: args.extras if v is None else v
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -755,6 +817,7 @@ def main():
             ok = ok and ident and total == bytes(32)
             rlc_state["total"] = total.hex()
         rlc_state["ok"] = rlc_state["ok"] and ok
+        rlc_state["last"] = (partial, ok)
 
     step = step_each if args.mode == "each" else step_rlc
 
@@ -787,6 +850,31 @@ def main():
     n_bad = int((status != 0).sum().item())
     if n_bad or not rlc_state["ok"]:
         raise SystemExit("bench: %d proofs rejected (or not written) in the timed region" % n_bad)
+
+    if args.dump_outputs:
+        outs = {"status": status.cpu().numpy()}
+        if args.mode == "rlc":
+            partial, ok = rlc_state["last"]
+            outs["partial"] = np.frombuffer(partial, np.uint8)
+            outs["ok"] = np.array([bool(ok)], np.uint8)
+        # Valid proofs give all-zero statuses and the identity as the partial, which tell two
+        # builds apart only when one of them is broken outright.  So the same call runs once
+        # more, untimed, on a copy of the inputs with PROBE_ROWS fixed rows spoiled (probe_*).
+        p, p_rows = probe_inputs(torch, t, n)
+        p_st = torch.full_like(status, 0xFF)
+        if args.mode == "each":
+            gpu.verify_each_device(p["y1"], p["y2"], p["r1"], p["r2"], p["s"], p_st, stream=stream, **cx)
+        else:
+            partial, ok = gpu.verify_batch_device(p["y1"], p["y2"], p["r1"], p["r2"], p["s"], p_st, WEIGHT_SEED,
+                                                  first_index=lo, stream=stream, **cx)
+            outs["probe_partial"] = np.frombuffer(partial, np.uint8)
+            outs["probe_ok"] = np.array([bool(ok)], np.uint8)
+        torch.cuda.synchronize(dev)
+        outs["probe_status"] = p_st.cpu().numpy()
+        outs["probe_rows"] = p_rows   # the spoiled rows and their statuses, whatever a long array's sample holds
+        outs["probe_status_at_rows"] = outs["probe_status"][p_rows]
+        del p, p_st
+        dump_outputs(args.dump_outputs, outs, rank, world)
 
     oc = _load_json("bench/opcount.json") or {}
     peak_mad = oc.get("peaks", {}).get("v_mad_i64_i32_lane_ops_per_s", 28.32e12)

@@ -7,8 +7,8 @@ use it, and only as the checker.
 
 It restates, in plain Python integers, what the reference computes on the
 verify path.  The reference (Rust, kobby-pentangeli/chaum-pedersen-zkp) keeps
-all arithmetic in third-party crates that are not vendored under
-/root/reference and cannot be built here (no cargo/rustc); their published
+all arithmetic in third-party crates that are not vendored with it and
+cannot be built without a Rust toolchain; their published
 algorithms are restated instead:
 
 * curve25519-dalek 4.1.3 (Cargo.lock:607-619) -> ristretto255 per RFC 9496

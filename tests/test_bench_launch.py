@@ -114,3 +114,24 @@ def test_cpu_threads_capped_at_cgroup_quota(monkeypatch):
     monkeypatch.setattr(bench, "_cgroup_cpu_quota", lambda: 0.5)
     assert bench.cpu_threads(0)["threads"] == 1
     assert bench.cpu_threads(3)["threads"] == 3
+
+
+def test_dump_outputs_writes_float32_and_samples_long_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: every array lands as <name>.npy in float32; one longer than DUMP_MAX_ROWS is
+    cut to the same sorted sample of rows on every call, whose indices are written beside it."""
+    import numpy as np
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 100)
+    status = (np.arange(1000) % 7).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"status": status, "partial": np.arange(32, dtype=np.uint8)})
+    got = {f: np.load(str(tmp_path / "a" / f)) for f in sorted(os.listdir(str(tmp_path / "a")))}
+    assert sorted(got) == ["partial.npy", "status.npy", "status_rows.npy"]
+    assert got["partial.npy"].dtype == np.float32 and got["partial.npy"].tolist() == list(range(32))
+    rows = got["status_rows.npy"].astype(np.int64)
+    assert len(rows) == 100 and (np.diff(rows) > 0).all() and rows[-1] < 1000
+    assert got["status.npy"].dtype == np.float32 and np.array_equal(got["status.npy"], status[rows])
+    for f in got:
+        assert np.array_equal(got[f], np.load(str(tmp_path / "b" / f)))
+    bench.dump_outputs(str(tmp_path / "c"), {"status": status[:5]}, rank=1, world=2)
+    assert os.listdir(str(tmp_path / "c")) == ["status_rank1.npy"]

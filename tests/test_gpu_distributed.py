@@ -203,8 +203,8 @@ def test_bench_rlc_four_rank_rehearsal(launcher):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     args = ["--gpus", "4", "--mode", "rlc", "--n-total", str(1 << 20), "--same-device", "--backend", "gloo",
-            "--steps", "1", "--warmup", "1", "--extras", "0", "--no-cpu-baseline", "--c4-n", str(1 << 21),
-            "--c4-steps", "1"]
+            "--steps", "1", "--warmup", "1", "--full", "--extras", "0", "--no-cpu-baseline",
+            "--c4-n", str(1 << 21), "--c4-steps", "1"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")] + args
@@ -233,8 +233,8 @@ def test_bench_rlc_four_rank_rehearsal(launcher):
     # one process computes over the whole 2^21 proofs (weights keyed by the global index)
     if launcher == "none":
         one = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "rlc", "--n-total", str(1 << 20),
-               "--steps", "1", "--warmup", "1", "--extras", "0", "--no-cpu-baseline", "--c4-n", str(1 << 21),
-               "--c4-steps", "1"]
+               "--steps", "1", "--warmup", "1", "--full", "--extras", "0", "--no-cpu-baseline",
+               "--c4-n", str(1 << 21), "--c4-steps", "1"]
         r1 = subprocess.run(one, capture_output=True, text=True, timeout=360, env=env, cwd=ROOT)
         assert r1.returncode == 0, r1.stderr[-3000:]
         d1 = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][0])

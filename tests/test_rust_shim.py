@@ -106,7 +106,6 @@ def test_reference_patch_is_safe_code():
             assert "SAFETY" in ctx, (i, l)
 
 
-REF_BATCH = "/root/reference/src/verifier/batch.rs"
 VERIFY_SIG = "pub fn verify<R: CryptoRngCore>(&self, rng: &mut R) -> Result<Vec<Result<()>>>"
 
 
@@ -117,13 +116,10 @@ def _code(rel):
 
 def test_patch_serves_verify_with_the_reference_signature():
     """The drop-in is `verify` itself (batch.rs:171), not a new method: callers need no edit.
-    Its signature is the reference's (read from the reference when it is present), and it
-    dispatches to the GPU under the feature and to the renamed CPU body otherwise."""
+    Its signature is the reference's (VERIFY_SIG, pinned here), and it dispatches to the GPU
+    under the feature and to the renamed CPU body otherwise."""
     d = _code("rust/reference-patch/dispatch.rs")
     assert " ".join(d.split()).count(VERIFY_SIG) == 1
-    if os.path.exists(REF_BATCH):
-        ref = " ".join(open(REF_BATCH).read().split())
-        assert VERIFY_SIG in ref
     assert '#[cfg(feature = "gpu")]' in d and "super::gpu::verify(self, rng)" in d
     assert '#[cfg(not(feature = "gpu"))]' in d and "self.verify_cpu(rng)" in d
     g = _code("rust/reference-patch/gpu.rs")

@@ -17,8 +17,8 @@ buckets in ascending order: E (run += entry) per entry, B (acc += run) per bucke
 Usage: python3 tools/c5_walk_sim.py [blocks] > profiles/rNN_c5_walk_sim.json
 """
 import json
-import random, sys
-sys.path.insert(0, '/root/repo/tools')
+import os, random, sys
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from part_entries import recode16, split8, L
 
 def block_digits(rng, proofs=128):

@@ -1,7 +1,8 @@
 """One small synchronous call repeated (N proofs; MODE=batch: cpz_verify_batch, MODE=each:
 cpz_verify_each), for a kernel / copy trace of the drop-in's regime under rocprofv3."""
 import os, sys, time
-sys.path.insert(0, "/root/repo/chaum-pedersen-zkp_amd"); sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "chaum-pedersen-zkp_amd")); sys.path.insert(0, ROOT)
 import numpy as np
 import bench
 import chaum_pedersen as cp
