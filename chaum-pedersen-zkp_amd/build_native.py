@@ -149,6 +149,22 @@ def build_dropin_test(force: bool = False) -> str:
     return DROPIN_TEST
 
 
+MERGE_TEST = os.path.join(ROOT, "tests", "cpp", "merge_groups_test")
+
+
+def build_merge_groups_test(force: bool = False) -> str:
+    """The C++ mirror's merged dispatch against its per-group one (tests/test_gpu_pairs_cpp.py)."""
+    src = os.path.join(ROOT, "tests", "cpp", "merge_groups_test.cpp")
+    hdrs = [os.path.join(ROOT, "include", "cpz.h"), os.path.join(ROOT, "include", "cpz_batch.hpp")]
+    if not force and not _newer(MERGE_TEST, [src] + hdrs):  # libcpz.so: linked dynamically
+        return MERGE_TEST
+    cxx = shutil.which("g++") or "g++"
+    _run([cxx, "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", MERGE_TEST + ".tmp",
+          "-L", LIBDIR, "-lcpz", "-Wl,-rpath,$ORIGIN/../../chaum-pedersen-zkp_amd/lib"])
+    os.replace(MERGE_TEST + ".tmp", MERGE_TEST)
+    return MERGE_TEST
+
+
 def build_oracle(force: bool = False) -> None:
     mk = os.path.join(ROOT, "oracle", "Makefile")
     if os.path.exists(mk):
@@ -161,6 +177,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_libcpz(force, verbose)
     build_cpp_test(force)
     build_dropin_test(force)
+    build_merge_groups_test(force)
 
 
 if __name__ == "__main__":

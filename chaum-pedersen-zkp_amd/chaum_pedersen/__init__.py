@@ -272,6 +272,19 @@ def _ctx_arrays(contexts: Optional[Sequence[Optional[bytes]]], n: int):
     return blob, off, present
 
 
+def _pair_indices(pair_idx, n: int, npairs: int) -> np.ndarray:
+    """pair_idx of Gpu.verify_each_pairs as uint32[n]: n integers, each in [0, npairs)."""
+    a = np.asarray(pair_idx)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise InvalidParams("pair_idx must hold one index per proof: shape %s for %d proofs" % (a.shape, n))
+    if n and not (np.issubdtype(a.dtype, np.integer) and a.dtype != np.bool_):
+        raise InvalidParams("pair_idx must be integers, not %s" % a.dtype)
+    if n and (int(a.min()) < 0 or int(a.max()) >= npairs):
+        bad = int(np.nonzero((a < 0) | (a >= npairs))[0][0])
+        raise InvalidParams("pair_idx[%d] = %d is outside the %d pairs" % (bad, int(a[bad]), npairs))
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
 def _ptr(a) -> Optional[int]:
     return None if a is None else a.ctypes.data
 
@@ -373,6 +386,25 @@ class Gpu:
         _native.check(self._lib.cpz_verify_each_ex(
             self._h, _flags(equations_only), params.g, params.h, n, *[_ptr(a) for a in arrs], _ptr(blob), _ptr(off),
             _ptr(present), _ptr(out)))
+        return out
+
+    def verify_each_pairs(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, contexts=None,
+                          equations_only: bool = False) -> np.ndarray:
+        """Status per proof (uint8[n]) where entry i is verified under pairs[pair_idx[i]], all in
+        one call and one verify launch (cpz_verify_each_pairs_ex): at most PAIRS_MAX pairs and
+        PAIRS_MAX_PROOFS proofs.  Each status is what verify_each returns for that entry under
+        its own pair.  pair_idx: n integers in [0, len(pairs)), checked here before the library
+        is called."""
+        n = len(y1)
+        npairs = len(pairs)
+        idx = _pair_indices(pair_idx, n, npairs)
+        arrs = [_rows(a, n, nm) for a, nm in ((y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2"), (s, "s"))]
+        gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+        blob, off, present = _ctx_arrays(contexts, n)
+        out = np.empty(n, dtype=np.uint8)
+        _native.check(self._lib.cpz_verify_each_pairs_ex(
+            self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
+            _ptr(off), _ptr(present), _ptr(out)))
         return out
 
     def challenges(self, y1, y2, r1, r2, contexts=None, params: Optional[Parameters] = None) -> np.ndarray:
@@ -769,7 +801,12 @@ class BatchVerifier:
         (rust/reference-patch/gpu.rs; C++ mirror: include/cpz_batch.hpp): entries grouped by
         Parameters in order of first appearance; groups take consecutive weight indices, and a
         group of at least rlc_min_group entries (default RLC_MIN_GROUP) runs the RLC batch check
-        with its exact fallback (cpz_verify_batch), a smaller one cpz_verify_each.
+        with its exact fallback (cpz_verify_batch), a smaller one cpz_verify_each.  Unlike gpu.rs,
+        which issues one synchronous call per group, two or more smaller groups go out together
+        as one cpz_verify_each_pairs call (one verify launch, every entry under its own pair's
+        tables; one call per 64 pairs should there be more); a single smaller group keeps
+        cpz_verify_each.  The weight indices, the rng draws and every returned status are the
+        per-group sequence's.
 
         `rng` is drawn exactly as the reference draws it: nothing for a one-entry batch
         (verify_one, batch.rs:178-180), otherwise one 64-byte random_scalar per entry
@@ -806,17 +843,48 @@ class BatchVerifier:
             seed = draws[0][:32]
         elif uses_rlc:
             seed = os.urandom(32)
-        first_index = 0
-        for (g, h), idx in groups.items():
+        def rows_of(idx):
             ents = [self._entries[i] for i in idx]
             rows = [np.frombuffer(b"".join(getattr(e.statement if q in ("y1", "y2") else e.proof, q) for e in ents),
                                   np.uint8).reshape(-1, 32) for q in ("y1", "y2", "r1", "r2", "s")]
-            ctxs = [e.context for e in ents]
+            return rows, [e.context for e in ents]
+
+        per_proof = [(gh, idx) for gh, idx in groups.items() if len(idx) < rlc_min]
+        merge = len(per_proof) >= 2
+        first_index = 0
+        for (g, h), idx in groups.items():
             if len(idx) >= rlc_min:
+                rows, ctxs = rows_of(idx)
                 _, _, st = gpu.verify_batch(*rows, seed, first_index=first_index, contexts=ctxs,
                                             params=Parameters(g, h), equations_only=True)
-            else:
-                st = gpu.verify_each(*rows, contexts=ctxs, params=Parameters(g, h), equations_only=True)
+                status[np.array(idx)] = st
+            elif not merge:
+                rows, ctxs = rows_of(idx)
+                status[np.array(idx)] = gpu.verify_each(*rows, contexts=ctxs, params=Parameters(g, h),
+                                                        equations_only=True)
             first_index += len(idx)
-            status[np.array(idx)] = st
+        if merge:
+            # the per-proof groups in one call per PAIRS_MAX pairs (and PAIRS_MAX_PROOFS entries),
+            # entries in batch order
+            calls, cur, cur_n = [], [], 0
+            for gh, idx in per_proof:
+                if cur and (len(cur) == _native.PAIRS_MAX or cur_n + len(idx) > _native.PAIRS_MAX_PROOFS):
+                    calls.append(cur)
+                    cur, cur_n = [], 0
+                cur.append((gh, idx))
+                cur_n += len(idx)
+            calls.append(cur)
+            for call in calls:
+                if len(call) == 1:   # a chunk's lone group: the single-pair call
+                    (g, h), idx = call[0]
+                    rows, ctxs = rows_of(idx)
+                    status[np.array(idx)] = gpu.verify_each(*rows, contexts=ctxs, params=Parameters(g, h),
+                                                            equations_only=True)
+                    continue
+                which = {i: p for p, (_, idx) in enumerate(call) for i in idx}
+                order = sorted(which)
+                rows, ctxs = rows_of(order)
+                status[np.array(order)] = gpu.verify_each_pairs(
+                    [Parameters(g, h) for (g, h), _ in call], np.array([which[i] for i in order], np.uint32), *rows,
+                    contexts=ctxs, equations_only=True)
         return [VerifyResult(s) for s in status]

@@ -167,6 +167,27 @@ struct VerifyArgs {
                                     // k_verify_quad only (launches of at most quad_max proofs)
 };
 
+// Mixed-pair calls (cpz_verify_each_pairs): proof i verifies under desc[pair_idx[i]] -- the
+// pair's Niels tables as variable bases (VerifyArgs::vtab / vtab16 of a single-pair call) and
+// what ChallengeArgs carries per (g, h): the two transcript prefixes, the generator words and
+// the fixed-schedule masks.  k_verify_wide_pairs / k_verify_small_pairs read these instead.
+struct PairDesc {
+  const ge_niels* tab;           // GenSet::tab
+  const int32_t* tab16;          // GenSet::tab16
+  StrobeSnap prefix[2];          // [0] after Transcript::new(), [1] after append_parameters
+  uint32_t gh_words[16];
+  int32_t fast_noctx;            // ChallengeArgs::fast_noctx with k1 / k2
+  int32_t fast_ctx32;            // ChallengeArgs::fast_ctx32 with c32
+  uint32_t k1[50];
+  uint32_t k2[50];
+  uint32_t c32[3][50];
+};
+static_assert(sizeof(PairDesc) % 16 == 0, "descriptor rows stay 16-byte aligned");
+struct PairArgs {
+  const PairDesc* desc = nullptr;      // the call's pairs (host-checked: every index below is in range)
+  const uint32_t* pair_idx = nullptr;  // n indices into desc
+};
+
 struct ProveArgs {
   int64_t n;
   uint64_t first_index;
@@ -204,6 +225,10 @@ hipError_t launch_verify_small(const VerifyArgs& a, const ChallengeArgs& ca, hip
 // one proof per workgroup of six waves (4 + CPZ_WIDE_VB_WAVES = eight with vtab16), field products
 // on 16-lane rows (fe16.h)
 hipError_t launch_verify_wide(const VerifyArgs& a, const ChallengeArgs& ca, hipStream_t st);
+// The same two kernels with a pair per proof (PairArgs): a.comb / a.vtab / a.vtab16 and ca's
+// prefix, gh_words and masks are unused, every proof takes its pair's variable-base tables.
+hipError_t launch_verify_small_pairs(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa, hipStream_t st);
+hipError_t launch_verify_wide_pairs(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa, hipStream_t st);
 int verify_each_blocks_per_cu();  // resident k_verify_each blocks per CU (occupancy API)
 hipError_t launch_prove_points(const ProveArgs& a, hipStream_t st);
 hipError_t launch_prove_response(const ProveArgs& a, hipStream_t st);

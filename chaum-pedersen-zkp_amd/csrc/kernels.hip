@@ -854,7 +854,11 @@ struct SmallShared {
   uint32_t sponge[50][kSmallProofs];   // wave 2's byte-wise transcript, one column per proof
 };
 
-__global__ void __launch_bounds__(64 * 3) k_verify_small(VerifyArgs a, ChallengeArgs ca) {
+// kPairs (k_verify_small_pairs): proof ii verifies under pa.desc[pa.pair_idx[ii]], so the pair
+// differs from quad to quad: wave 2 takes its transcript data, gt / gt2 per proof from there,
+// always as variable bases.  Dead slots run entry 0's pair.
+template <bool kPairs>
+__device__ __forceinline__ void verify_small_body(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa) {
   __shared__ SmallShared sh;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int j = l >> 3, quad = l >> 2, e = (l >> 2) & 1, q = l & 3;
@@ -915,7 +919,9 @@ __global__ void __launch_bounds__(64 * 3) k_verify_small(VerifyArgs a, Challenge
   } else {
     // ---- wave 2: challenge, response checks, split, digits ------------------------------
     uint32_t dg[16], meta;
-    proof_digits(dg, meta, a, ca, ii, (l & 7) == 0, &sh.sponge[0][0], j, kSmallProofs);
+    const PairDesc* pd = nullptr;
+    if constexpr (kPairs) pd = pa.desc + pa.pair_idx[ii];
+    proof_digits<false, kPairs>(dg, meta, a, ca, ii, (l & 7) == 0, &sh.sponge[0][0], j, kSmallProofs, nullptr, pd);
     if ((l & 7) == 0) {
 #pragma unroll
       for (int k = 0; k < 16; k++) sh.dig[j][k] = dg[k];
@@ -928,9 +934,11 @@ __global__ void __launch_bounds__(64 * 3) k_verify_small(VerifyArgs a, Challenge
 #pragma unroll
     for (int k = 0; k < 8; k++) sd[k] = sh.dig[j][8 + k];
     // ---- [s'] B of equation e -------------------------------------------------------------
-    if (a.vtab) {  // variable bases: 16 radix-256 windows of s' on B and of s' >> 128 on 2^128 B
-      const ge_niels* gt = a.vtab + e * kNielsEntries;
-      const ge_niels* gt2 = a.vtab + (2 + e) * kNielsEntries;
+    if (kPairs || a.vtab) {  // variable bases: 16 radix-256 windows of s' on B and of s' >> 128 on 2^128 B
+      const ge_niels* vt = a.vtab;
+      if constexpr (kPairs) vt = pd->tab;
+      const ge_niels* gt = vt + e * kNielsEntries;
+      const ge_niels* gt2 = vt + (2 + e) * kNielsEntries;
 #pragma unroll 1
       for (int b = 15; b >= 0; b--) {
         const int dg = (int32_t)(sd[b >> 2] << (24 - 8 * (b & 3))) >> 24;
@@ -982,6 +990,22 @@ __global__ void __launch_bounds__(64 * 3) k_verify_small(VerifyArgs a, Challenge
   if (stamps) stamps[10] = __builtin_amdgcn_s_memrealtime();
 #endif
 #undef CPZ_SMALL_STAMP
+}
+
+__global__ void __launch_bounds__(64 * 3) k_verify_small(VerifyArgs a, ChallengeArgs ca) {
+  verify_small_body<false>(a, ca, PairArgs{});
+}
+
+__global__ void __launch_bounds__(64 * 3) k_verify_small_pairs(VerifyArgs a, ChallengeArgs ca, PairArgs pa) {
+  verify_small_body<true>(a, ca, pa);
+}
+
+hipError_t launch_verify_small_pairs(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.pre || a.blocks || a.c || !pa.desc || !pa.pair_idx) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_verify_small_pairs, dim3((unsigned)((a.n + kSmallProofs - 1) / kSmallProofs)), dim3(64 * 3), 0,
+                     st, a, ca, pa);
+  return hipGetLastError();
 }
 
 hipError_t launch_verify_small(const VerifyArgs& a, const ChallengeArgs& ca, hipStream_t st) {

@@ -74,11 +74,16 @@ struct LdsState {
 // run on every lane; any other context runs the byte-wise sponge on the lanes with
 // `sponge_lane` set, on column `col` of the LDS image `sponge` (50 x ncols words) -- the other
 // lanes' results are then meaningless and the caller takes the sponge lane's from LDS.
-template <bool kWave = false>
+// kPairs: the transcript prefixes, generator words and fixed-schedule masks are the proof's own
+// pair's (pd, a PairDesc) instead of ca's, and s' is always recoded for variable bases.
+template <bool kWave = false, bool kPairs = false>
 __device__ __forceinline__ void proof_digits(uint32_t dig[16], uint32_t& meta, const VerifyArgs& a,
                                              const ChallengeArgs& ca, int64_t ii, bool sponge_lane,
                                              uint32_t* sponge, int col, int ncols,
-                                             uint64_t* stamp_challenge = nullptr) {
+                                             uint64_t* stamp_challenge = nullptr, const PairDesc* pd = nullptr) {
+  // each is read where the single-pair code reads ca's field (kPairs is a constant: one arm is
+  // compiled), so the single-pair instantiations stay what they were
+#define CPZ_PAIR_FIELD(f) (kPairs ? pd->f : ca.f)
   uint32_t sw[8], cw[8];
   load_words8(sw, a.s, ii);
   uint8_t st_s;
@@ -93,37 +98,37 @@ __device__ __forceinline__ void proof_digits(uint32_t dig[16], uint32_t& meta, c
     load_words8(r2, a.r2, ii);
     const bool has_ctx = ca.ctx_off != nullptr && (ca.ctx_present == nullptr || ca.ctx_present[ii] != 0);
     const uint64_t b0 = has_ctx ? ca.ctx_off[ii] : 0, b1 = has_ctx ? ca.ctx_off[ii + 1] : 0;
-    const bool fixed_noctx = !has_ctx && ca.fast_noctx;
-    const bool fixed_ctx32 = has_ctx && ca.fast_ctx32 && b1 - b0 == 32 &&
+    const bool fixed_noctx = !has_ctx && CPZ_PAIR_FIELD(fast_noctx);
+    const bool fixed_ctx32 = has_ctx && CPZ_PAIR_FIELD(fast_ctx32) && b1 - b0 == 32 &&
                              ((reinterpret_cast<uintptr_t>(ca.ctx_bytes) + b0) & 3) == 0;
     sc c;
     if (fixed_noctx) {
-      const uint32_t* pre = reinterpret_cast<const uint32_t*>(ca.prefix[1].state);
+      const uint32_t* pre = reinterpret_cast<const uint32_t*>(CPZ_PAIR_FIELD(prefix)[1].state);
       if constexpr (kWave)
-        c = challenge_fixed(pre, ca.k1, ca.k2, y1, y2, r1, r2, PermRows{sponge, (int)(threadIdx.x & 63)});
+        c = challenge_fixed(pre, CPZ_PAIR_FIELD(k1), CPZ_PAIR_FIELD(k2), y1, y2, r1, r2, PermRows{sponge, (int)(threadIdx.x & 63)});
       else
-        c = challenge_fixed(pre, ca.k1, ca.k2, y1, y2, r1, r2);
+        c = challenge_fixed(pre, CPZ_PAIR_FIELD(k1), CPZ_PAIR_FIELD(k2), y1, y2, r1, r2);
     } else if (fixed_ctx32) {
       uint32_t cx[8];
       const uint32_t* cp = reinterpret_cast<const uint32_t*>(ca.ctx_bytes + b0);
 #pragma unroll
       for (int k = 0; k < 8; k++) cx[k] = cp[k];
-      const uint32_t* pre = reinterpret_cast<const uint32_t*>(ca.prefix[0].state);
+      const uint32_t* pre = reinterpret_cast<const uint32_t*>(CPZ_PAIR_FIELD(prefix)[0].state);
       if constexpr (kWave)
-        c = challenge_fixed_ctx32(pre, ca.c32, cx, y1, y2, r1, r2, PermRows{sponge, (int)(threadIdx.x & 63)});
+        c = challenge_fixed_ctx32(pre, CPZ_PAIR_FIELD(c32), cx, y1, y2, r1, r2, PermRows{sponge, (int)(threadIdx.x & 63)});
       else
-        c = challenge_fixed_ctx32(pre, ca.c32, cx, y1, y2, r1, r2);
+        c = challenge_fixed_ctx32(pre, CPZ_PAIR_FIELD(c32), cx, y1, y2, r1, r2);
     } else {
       for (int k = 0; k < 8; k++) c.w[k] = 0;
       if (sponge_lane) {
         LdsState lst{sponge, col, ncols};
-        const StrobeSnap& snap = ca.prefix[has_ctx ? 0 : 1];
+        const StrobeSnap& snap = CPZ_PAIR_FIELD(prefix)[has_ctx ? 0 : 1];
         const uint32_t* src = reinterpret_cast<const uint32_t*>(snap.state);
         for (int k = 0; k < 50; k++) sponge[k * ncols + col] = src[k];
         Strobe<LdsState> st(lst, snap.pos, snap.pos_begin, (uint8_t)snap.flags);
         if (has_ctx) {
           transcript_context(st, ca.ctx_bytes + b0, (uint32_t)(b1 - b0));
-          transcript_parameters(st, ca.gh_words, ca.gh_words + 8);
+          transcript_parameters(st, CPZ_PAIR_FIELD(gh_words), CPZ_PAIR_FIELD(gh_words) + 8);
         }
         c = transcript_challenge(st, y1, y2, r1, r2);
       }
@@ -154,11 +159,12 @@ __device__ __forceinline__ void proof_digits(uint32_t dig[16], uint32_t& meta, c
   }
   sc sp = sc_mul(vs, ss);
   if (vneg) sp = sc_neg(sp);
-  if (a.vtab)
+  if (kPairs || a.vtab)
     sc_recode_radix256(dig + 8, sp.w);
   else
     sc_recode_radix65536(dig + 8, sp.w);
   meta = (vneg ? 1u : 0u) | ((uint32_t)st_s << 8);
+#undef CPZ_PAIR_FIELD
 }
 
 }  // namespace cpz

@@ -179,6 +179,7 @@ struct GenSet {
   DevBuf comb;      // fixed-base combs of g and h: 2 x 16 x 2^15 ge_niels (128 MiB)
   DevBuf comb_q;    // 32 ge_p3: 2^(16 k) g, 2^(16 k) h
   DevBuf prefix;    // 2 StrobeSnap
+  cpz::StrobeSnap snap[2];  // their host copy (a mixed-pair call's descriptor, pair_desc)
   DevBuf gh_words;  // 16 words
   bool prefix_fixed = false;  // prefix[1] at the fixed position: k_challenge_noctx applies
   uint32_t chal_k1[50], chal_k2[50];  // its framing masks
@@ -384,9 +385,9 @@ int build_niels_prefix(cpz_ctx* ctx, GenSet& e, const uint8_t both[64]) {
   CPZ_HIP(cpz::launch_transcript_prefix(static_cast<const uint32_t*>(e.gh_words.p),
                                         static_cast<cpz::StrobeSnap*>(e.prefix.p), ctx->stream));
   int ok[2] = {0, 0};
-  cpz::StrobeSnap snap[2];
+  cpz::StrobeSnap* const snap = e.snap;
   CPZ_HIP(hipMemcpyAsync(ok, ctx->ok_flags.p, sizeof(ok), hipMemcpyDeviceToHost, ctx->stream));
-  CPZ_HIP(hipMemcpyAsync(snap, e.prefix.p, sizeof(snap), hipMemcpyDeviceToHost, ctx->stream));
+  CPZ_HIP(hipMemcpyAsync(snap, e.prefix.p, sizeof(e.snap), hipMemcpyDeviceToHost, ctx->stream));
   CPZ_HIP(hipStreamSynchronize(ctx->stream));
   if (!ok[0] || !ok[1]) return fail(CPZ_EGENERATOR, "generator encoding does not decode to a ristretto255 point");
   e.prefix_fixed = cpz::challenge_prefix_is_fixed(snap[1]) && cpz::challenge_masks(e.chal_k1, e.chal_k2);
@@ -403,7 +404,10 @@ int build_niels_prefix(cpz_ctx* ctx, GenSet& e, const uint8_t both[64]) {
 // Otherwise the least recently used full set (an unused one first) is rebuilt: k_build_niels,
 // k_transcript_prefix and the 128 MiB combs (~3 ms), timed as stage 7.  If the combs do not fit,
 // the other full sets are freed and the allocation is tried once more.
-int ensure_generators(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], bool need_comb = true) {
+// any_light (a mixed-pair call, which reads every pair's Niels tables and builds no comb): the
+// default pair without a cached full set takes a light set like any other.
+int ensure_generators(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], bool need_comb = true,
+                      bool any_light = false) {
   uint8_t both[64];
   std::memcpy(both, g, 32);
   std::memcpy(both + 32, h, 32);
@@ -415,7 +419,7 @@ int ensure_generators(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], bo
       return CPZ_OK;
     }
   }
-  const bool light = !need_comb && !is_default_pair(g, h);
+  const bool light = !need_comb && (any_light || !is_default_pair(g, h));
   if (light) {
     for (GenSet& e : ctx->light) {
       if (e.valid && std::memcmp(e.gh, both, 64) == 0) {
@@ -568,8 +572,10 @@ int join_verify_streams(cpz_ctx* ctx, hipStream_t st) {
 
 // ca != nullptr: each chunk's challenges are computed on the chunk's own stream right before
 // its verify launch (so they overlap the other stream's verify work) instead of up front.
+// pairs != nullptr (cpz_verify_each_pairs, at most kSmallMax proofs): the latency kernels' mixed-
+// pair siblings, every proof under its own pair's tables.
 int launch_verify_chunks(cpz_ctx* ctx, const cpz::VerifyArgs& va, int stage, hipStream_t st, VerifyRR* rr,
-                         bool join, const cpz::ChallengeArgs* ca = nullptr) {
+                         bool join, const cpz::ChallengeArgs* ca = nullptr, const cpz::PairArgs* pairs = nullptr) {
   static_assert(CPZ_VERIFY_STREAMS >= 1 && CPZ_VERIFY_STREAMS <= 4, "1..4 verify streams");
   const int full = verify_full_grid(ctx);
   const int grid = std::min(full, verify_grid(ctx, (size_t)va.n));
@@ -620,12 +626,21 @@ int launch_verify_chunks(cpz_ctx* ctx, const cpz::VerifyArgs& va, int stage, hip
         v.c = nullptr;  // computed in the kernel
       }
       StageTimer t(ctx, stage, sc);
-      if (v.n <= wide_max())  // a light set always carries vtab16 beside vtab (build_niels_prefix)
+      if (pairs) {
+        cpz::PairArgs pp = *pairs;
+        pp.pair_idx += a;
+        if (v.n <= wide_max())
+          CPZ_HIP(cpz::launch_verify_wide_pairs(v, cc, pp, sc));
+        else
+          CPZ_HIP(cpz::launch_verify_small_pairs(v, cc, pp, sc));
+      } else if (v.n <= wide_max()) {  // a light set always carries vtab16 beside vtab (build_niels_prefix)
         CPZ_HIP(cpz::launch_verify_wide(v, cc, sc));
-      else
+      } else {
         CPZ_HIP(cpz::launch_verify_small(v, cc, sc));
+      }
       continue;
     }
+    if (pairs) return fail(CPZ_EINVAL, "internal: mixed-pair call outside the latency kernels' range");
     if (ca) {
       cpz::ChallengeArgs cc = *ca;
       cc.n = v.n;
@@ -713,7 +728,8 @@ inline size_t pad16(size_t x) { return (x + 15) & ~size_t(15); }
 int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count, const uint8_t* ctx_bytes,
                  const uint64_t* ctx_off, const uint8_t* ctx_present, const void* dev[5], const void** dcb,
                  const uint64_t** dco, const uint8_t** dcp, bool direct = false, uint8_t** status_dev = nullptr,
-                 uint8_t** status_host = nullptr) {
+                 uint8_t** status_host = nullptr, const void* extra = nullptr, size_t extra_bytes = 0,
+                 const void** dextra = nullptr) {
   if (status_dev) *status_dev = nullptr;
   if (ctx_off)
     for (size_t i = 0; i < n; i++)
@@ -722,7 +738,11 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
   const size_t rows = (size_t)count * n * 32;
   const size_t o_off = rows, o_pres = pad16(o_off + (ctx_off ? (n + 1) * 8 : 0));
   const size_t o_ctx = pad16(o_pres + (ctx_off && ctx_present ? n : 0));
-  const size_t total = pad16(o_ctx + (ctx_off ? std::max<size_t>(nbytes, 1) : 0));
+  // extra (a mixed-pair call's descriptor table and indices): packed after the contexts and
+  // always copied to the device, zero-copy or not -- every proof reads ~1.5 KB of it
+  const size_t o_extra = pad16(o_ctx + (ctx_off ? std::max<size_t>(nbytes, 1) : 0));
+  const size_t total = pad16(o_extra + extra_bytes);
+  if (dextra) *dextra = nullptr;
   // no copy of an earlier call may still read the block when it is rewritten or regrown
   // (host-buffer calls return synchronised; this covers one that failed part-way)
   if (total <= kPinStageMax) CPZ_HIP(hipStreamSynchronize(ctx->stream));
@@ -736,11 +756,16 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
       if (ctx_present) std::memcpy(h + o_pres, ctx_present, n);
       if (nbytes) std::memcpy(h + o_ctx, ctx_bytes + ctx_off[0], nbytes);
     }
+    if (extra_bytes) std::memcpy(h + o_extra, extra, extra_bytes);
     uint8_t* d = static_cast<uint8_t*>(ctx->in_all.p);
+    if (dextra && extra_bytes) *dextra = d + o_extra;
     if (direct && status_dev && status_host && ctx->pin.dp) {
       d = static_cast<uint8_t*>(ctx->pin.dp) + kPinMail;
       *status_dev = d + total;
       *status_host = h + total;
+      if (extra_bytes)
+        CPZ_HIP(hipMemcpyAsync(static_cast<uint8_t*>(ctx->in_all.p) + o_extra, h + o_extra, extra_bytes,
+                               hipMemcpyHostToDevice, ctx->stream));
     } else if (total) {
       CPZ_HIP(hipMemcpyAsync(ctx->in_all.p, h, total, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -759,6 +784,12 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
   *dcb = nullptr;
   *dco = nullptr;
   *dcp = nullptr;
+  if (extra_bytes) {
+    CPZ_HIP(ctx->in[5].ensure(extra_bytes));
+    CPZ_HIP(hipMemcpyAsync(ctx->in[5].p, extra, extra_bytes, hipMemcpyHostToDevice, ctx->stream));
+    CPZ_HIP(hipStreamSynchronize(ctx->stream));  // a pageable source: read before the caller frees it
+    if (dextra) *dextra = ctx->in[5].p;
+  }
   if (ctx_off) {
     std::vector<uint64_t> rel(n + 1);
     for (size_t i = 0; i <= n; i++) rel[i] = ctx_off[i] - ctx_off[0];
@@ -2230,6 +2261,138 @@ int cpz_verify_each_ex(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], const 
                       static_cast<uint8_t*>(ctx->st.p), ctx->stream);
   if (rc) return rc;
   // statuses through the page-locked block when stage_inputs used it (its inputs are spent)
+  const bool pinned = ctx->pin.cap >= kPinMail + pad16(n);
+  uint8_t* dst = pinned ? static_cast<uint8_t*>(ctx->pin.p) + kPinMail : status_out;
+  CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
+  CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (pinned) std::memcpy(status_out, dst, n);
+  return CPZ_OK;
+}
+
+namespace {
+
+// A resident set's row of a mixed-pair call's descriptor table (cpz::PairDesc).
+void pair_desc(cpz::PairDesc& d, const GenSet& e) {
+  d.tab = static_cast<const cpz::ge_niels*>(e.tab.p);
+  d.tab16 = static_cast<const int32_t*>(e.tab16.p);
+  std::memcpy(d.prefix, e.snap, sizeof(d.prefix));
+  words_from_bytes(d.gh_words, e.gh, e.gh + 32);
+  d.fast_noctx = e.prefix_fixed ? 1 : 0;
+  d.fast_ctx32 = e.ctx32_fixed ? 1 : 0;
+  std::memcpy(d.k1, e.chal_k1, sizeof(d.k1));
+  std::memcpy(d.k2, e.chal_k2, sizeof(d.k2));
+  std::memcpy(d.c32, e.chal_c32, sizeof(d.c32));
+}
+
+}  // namespace
+
+int cpz_verify_each_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const uint32_t* pair_idx,
+                          const uint8_t* y1, const uint8_t* y2, const uint8_t* r1, const uint8_t* r2, const uint8_t* s,
+                          const uint8_t* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present,
+                          uint8_t* status_out) {
+  return cpz_verify_each_pairs_ex(ctx, 0, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, ctx_bytes, ctx_off,
+                                  ctx_present, status_out);
+}
+
+int cpz_verify_each_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
+                             const uint32_t* pair_idx, const uint8_t* y1, const uint8_t* y2, const uint8_t* r1,
+                             const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                             const uint8_t* ctx_present, uint8_t* status_out) {
+  static_assert(CPZ_PAIRS_MAX <= kLightCache, "every pair of a call is resident at once");
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
+  if (npairs > CPZ_PAIRS_MAX)
+    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
+                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (n > CPZ_PAIRS_MAX_PROOFS || (int64_t)n > kSmallMax)
+    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_PAIRS_MAX_PROOFS (" +
+                                std::to_string(CPZ_PAIRS_MAX_PROOFS) + ")");
+  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !status_out)
+    return fail(CPZ_EINVAL, "null input pointer");
+  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  for (size_t i = 0; i < n; i++)
+    if (pair_idx[i] >= npairs)
+      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
+                                  " is not below npairs (" + std::to_string(npairs) + ")");
+  // Parameters::with_generators (gadgets.rs:77-103) for every pair before any table is built
+  static const uint8_t zero[32] = {0};
+  for (size_t p = 0; p < npairs; p++) {
+    const uint8_t *g = pairs + 64 * p, *h = g + 32;
+    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
+    if (std::memcmp(g, h, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
+  }
+  if (npairs == 1)
+    return cpz_verify_each_ex(ctx, flags, pairs, pairs + 32, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present,
+                              status_out);
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  // Every pair's set, full or light, resident at once: each is stamped as it is resolved, so
+  // with at most kLightCache pairs the least recently used light set is never this call's.
+  // The descriptor table and the indices go to the device in one block (stage_inputs' extra).
+  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
+  for (size_t p = 0; p < npairs; p++) {
+    int rc = ensure_generators(ctx, pairs + 64 * p, pairs + 64 * p + 32, false, true);
+    if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
+    cpz::PairDesc d;
+    pair_desc(d, *ctx->gs);
+    std::memcpy(extra.data() + p * sizeof(cpz::PairDesc), &d, sizeof(d));
+  }
+  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  int rc = order_after_last(ctx, ctx->stream);
+  if (rc) return rc;
+  const uint8_t* host[5] = {y1, y2, r1, r2, s};
+  const void* dev[5];
+  const void* dcb;
+  const uint64_t* dco;
+  const uint8_t* dcp;
+  const void* dex = nullptr;
+  uint8_t *st_dev = nullptr, *st_host = nullptr;
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, zero_copy(), &st_dev,
+                    &st_host, extra.data(), extra.size(), &dex);
+  if (rc) return rc;
+  if (!dex) return fail(CPZ_EHIP, "internal: the pair descriptors were not staged");
+  if (!st_dev) CPZ_HIP(ctx->st.ensure(n));
+  uint8_t* status = st_dev ? st_dev : static_cast<uint8_t*>(ctx->st.p);
+  cpz::ChallengeArgs ca{};
+  ca.eq_only = ctx->call_eq ? 1 : 0;
+  ca.n = (int64_t)n;
+  ca.y1 = static_cast<const uint32_t*>(dev[0]);
+  ca.y2 = static_cast<const uint32_t*>(dev[1]);
+  ca.r1 = static_cast<const uint32_t*>(dev[2]);
+  ca.r2 = static_cast<const uint32_t*>(dev[3]);
+  ca.s = static_cast<const uint32_t*>(dev[4]);
+  ca.ctx_bytes = static_cast<const uint8_t*>(dcb);
+  ca.ctx_off = dco;
+  ca.ctx_present = dcp;
+  ca.prefix = nullptr;  // per pair: PairDesc
+  ca.c_out = nullptr;
+  ca.status_out = status;
+  cpz::VerifyArgs va{};
+  va.n = (int64_t)n;
+  va.y1 = ca.y1;
+  va.y2 = ca.y2;
+  va.r1 = ca.r1;
+  va.r2 = ca.r2;
+  va.s = ca.s;
+  va.c = nullptr;  // computed in the kernel
+  va.status = status;
+  va.comb = nullptr;
+  va.eq_only = ca.eq_only;
+  cpz::PairArgs pa;
+  pa.desc = static_cast<const cpz::PairDesc*>(dex);
+  pa.pair_idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(dex) + npairs * sizeof(cpz::PairDesc));
+  {
+    StageTimer span(ctx, 5, ctx->stream);
+    if ((rc = launch_verify_chunks(ctx, va, 1, ctx->stream, nullptr, true, &ca, &pa))) return rc;
+  }
+  if (st_dev) {  // zero-copy: rows read and statuses written through the page-locked block
+    CPZ_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(status_out, st_host, n);
+    return CPZ_OK;
+  }
   const bool pinned = ctx->pin.cap >= kPinMail + pad16(n);
   uint8_t* dst = pinned ? static_cast<uint8_t*>(ctx->pin.p) + kPinMail : status_out;
   CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));

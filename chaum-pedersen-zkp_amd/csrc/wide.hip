@@ -65,7 +65,7 @@ __device__ __forceinline__ int niels16_b(const int32_t* t16, int d, const r16::L
 #define CPZ_WIDE_VB_WAVES 4
 #endif
 template <class Shared>
-__device__ __forceinline__ void wide_varbase(Shared& sh, const VerifyArgs& a, int e, int h, const r16::Lane& L) {
+__device__ __forceinline__ void wide_varbase(Shared& sh, const int32_t* vtab16, int e, int h, const r16::Lane& L) {
   constexpr int kParts = CPZ_WIDE_VB_WAVES == 4 ? 4 : 8;
   uint32_t sd[kParts];
 #pragma unroll
@@ -73,7 +73,7 @@ __device__ __forceinline__ void wide_varbase(Shared& sh, const VerifyArgs& a, in
   const int32_t* tq[kParts];
 #pragma unroll
   for (int k = 0; k < kParts; k++)
-    tq[k] = a.vtab16 + (size_t)(2 * kNielsLevelOfPart[kParts * h + k] + e) * kNielsEntries * 48;  // 2^(32 q) B_e
+    tq[k] = vtab16 + (size_t)(2 * kNielsLevelOfPart[kParts * h + k] + e) * kNielsEntries * 48;  // 2^(32 q) B_e
   r16::P4 acc = r16::identity(L);
 #pragma unroll 1
   for (int b = 3; b >= 0; b--) {
@@ -191,10 +191,16 @@ __device__ __forceinline__ void wide_comb(Shared& sh, const VerifyArgs& a, int h
   }
 }
 
-__global__ void __launch_bounds__(64 * (4 + CPZ_WIDE_VB_WAVES)) k_verify_wide(VerifyArgs a, ChallengeArgs ca) {
+// kPairs (k_verify_wide_pairs): the proof's pair comes from pa.desc[pa.pair_idx[i]] -- one proof
+// per workgroup, so the index is block-uniform and the descriptor's words are read with scalar
+// loads -- and [s'] g, [s'] h always run on the variable-base waves.
+template <bool kPairs>
+__device__ __forceinline__ void verify_wide_body(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa) {
   __shared__ WideShared sh;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int64_t i = blockIdx.x;
+  const PairDesc* pd = nullptr;
+  if constexpr (kPairs) pd = pa.desc + __builtin_amdgcn_readfirstlane((int)pa.pair_idx[i]);
   const r16::Lane L = r16::lane_of(l);
   r16::P4 acc = r16::identity(L);
   // Straus chain of each wave (0: Y_1, 1: R_1, 2: Y_2, 3: R_2); the challenge wave
@@ -269,9 +275,9 @@ __global__ void __launch_bounds__(64 * (4 + CPZ_WIDE_VB_WAVES)) k_verify_wide(Ve
     // ---- the challenge, response checks, split, digits -----------------------------------------
     uint32_t dg[16], meta;
 #if defined(CPZ_CLOCK_PROBE)
-    proof_digits<true>(dg, meta, a, ca, i, l == 0, sh.sponge, 0, 1, stamps ? stamps + 12 : nullptr);
+    proof_digits<true, kPairs>(dg, meta, a, ca, i, l == 0, sh.sponge, 0, 1, stamps ? stamps + 12 : nullptr, pd);
 #else
-    proof_digits<true>(dg, meta, a, ca, i, l == 0, sh.sponge, 0, 1);
+    proof_digits<true, kPairs>(dg, meta, a, ca, i, l == 0, sh.sponge, 0, 1, nullptr, pd);
 #endif
     if (l == 0) {
 #pragma unroll
@@ -291,16 +297,16 @@ __global__ void __launch_bounds__(64 * (4 + CPZ_WIDE_VB_WAVES)) k_verify_wide(Ve
     if (w == 1) CPZ_WIDE_STAMP(15);
   } else if (w == 4) {
     // ---- wave 4: [s'] B of both equations (comb on two quads, or the variable-base rows) --------
-    if (a.vtab16)
-      wide_varbase(sh, a, 0, 0, L);
+    if (kPairs || a.vtab16)
+      wide_varbase(sh, kPairs ? pd->tab16 : a.vtab16, 0, 0, L);
     else if (l < 8)
       wide_comb(sh, a, 0, l);
     CPZ_WIDE_STAMP(9);
   } else if (w >= 5) {
     // ---- waves 5.. : variable bases, wave 4 + e + 2 h takes half h of equation e; comb: wave 5
     // the second half of both equations' windows
-    if (a.vtab16)
-      wide_varbase(sh, a, (w - 4) & 1, (w - 4) >> 1, L);
+    if (kPairs || a.vtab16)
+      wide_varbase(sh, kPairs ? pd->tab16 : a.vtab16, (w - 4) & 1, (w - 4) >> 1, L);
     else if (w == 5 && l < 8)
       wide_comb(sh, a, 1, l);
   }
@@ -316,7 +322,7 @@ __global__ void __launch_bounds__(64 * (4 + CPZ_WIDE_VB_WAVES)) k_verify_wide(Ve
     R.T = sh.part[chain + 1][3][L.k];
     acc = r16::add_b(acc, r16::cached_b(r16::to_cached(R, L), false, L), L);
     r16::P4 S;
-    if (a.vtab16) {
+    if (kPairs || a.vtab16) {
       if (CPZ_WIDE_VB_WAVES == 4) {
         S.X = sh.sBv[e][1][0][L.k];
         S.Y = sh.sBv[e][1][1][L.k];
@@ -364,10 +370,26 @@ __global__ void __launch_bounds__(64 * (4 + CPZ_WIDE_VB_WAVES)) k_verify_wide(Ve
 #undef CPZ_WIDE_STAMP
 }
 
+__global__ void __launch_bounds__(64 * (4 + CPZ_WIDE_VB_WAVES)) k_verify_wide(VerifyArgs a, ChallengeArgs ca) {
+  verify_wide_body<false>(a, ca, PairArgs{});
+}
+
+__global__ void __launch_bounds__(64 * (4 + CPZ_WIDE_VB_WAVES)) k_verify_wide_pairs(VerifyArgs a, ChallengeArgs ca,
+                                                                                    PairArgs pa) {
+  verify_wide_body<true>(a, ca, pa);
+}
+
 hipError_t launch_verify_wide(const VerifyArgs& a, const ChallengeArgs& ca, hipStream_t st) {
   if (a.n <= 0) return hipSuccess;
   if (a.pre || a.blocks || (a.vtab && !a.vtab16) || (!a.vtab && !a.comb)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_verify_wide, dim3((unsigned)a.n), dim3(64 * (a.vtab16 ? 4 + CPZ_WIDE_VB_WAVES : 6)), 0, st, a, ca);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_wide_pairs(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.pre || a.blocks || a.c || !pa.desc || !pa.pair_idx) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_verify_wide_pairs, dim3((unsigned)a.n), dim3(64 * (4 + CPZ_WIDE_VB_WAVES)), 0, st, a, ca, pa);
   return hipGetLastError();
 }
 

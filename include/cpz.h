@@ -112,6 +112,32 @@ int cpz_verify_each_ex(cpz_ctx *ctx, uint32_t flags, const uint8_t g[32], const 
                        const uint8_t *s, const uint8_t *ctx_bytes, const uint64_t *ctx_off,
                        const uint8_t *ctx_present, uint8_t *status_out);
 
+/* Per-proof verification of n proofs whose entries carry their own generators, in one call
+ * and one verify launch: a BatchVerifier batch over several Parameters (batch.rs:52).
+ * `pairs` holds npairs rows of 64 bytes (g then h), pair_idx[i] < npairs names entry i's row,
+ * and status_out[i] is what cpz_verify_each_ex reports for entry i under that pair (every
+ * status, flag, commitment-check mode and context shape).  Rows may repeat and may be the
+ * default pair.  Every pair is verified from its 128-entry tables (a pair without cached
+ * tables gets a light set, stage 13; no combs are built), all resident at once -- hence
+ * CPZ_PAIRS_MAX, the light-set cache; CPZ_PAIRS_MAX_PROOFS is the latency kernels' bound.
+ * Checked before anything is launched, cpz_last_error naming the index or entry:
+ * n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_PAIRS_MAX, n > CPZ_PAIRS_MAX_PROOFS, a null
+ * pointer or a pair_idx[i] >= npairs -> CPZ_EINVAL; a pair that is the identity, has g == h
+ * or does not decode -> CPZ_EGENERATOR.  Host buffers only: the indices are checked on the
+ * host. */
+#define CPZ_PAIRS_MAX 64
+#define CPZ_PAIRS_MAX_PROOFS 2048
+int cpz_verify_each_pairs(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
+                          const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                          const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                          const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                          const uint8_t *ctx_present, uint8_t *status_out);
+int cpz_verify_each_pairs_ex(cpz_ctx *ctx, uint32_t flags, size_t npairs, const uint8_t *pairs, size_t n,
+                             const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                             const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                             const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                             const uint8_t *ctx_present, uint8_t *status_out);
+
 /* Same with device-resident, 16-byte aligned inputs/outputs, enqueued on `stream`
  * (a hipStream_t, or NULL for the context's own stream, which is a blocking stream and so
  * is ordered with the legacy default stream).  Does not synchronise.  Any later call on the

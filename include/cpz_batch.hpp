@@ -29,8 +29,12 @@
 // them (batch.rs:239-240), the first 32 keying every group's RLC check; groups take
 // consecutive weight indices (first_index), and a group of at least rlc_min_group entries runs
 // cpz_verify_batch_ex (RLC + exact fallback), a smaller one cpz_verify_each_ex.
+// set_merge_groups(true) (off by default, so the sequence above stays the drop-in's): two or
+// more smaller groups go out together as one cpz_verify_each_pairs_ex call per CPZ_PAIRS_MAX
+// groups -- one verify launch, every entry under its own pair -- with the same statuses.
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -290,10 +294,15 @@ class BatchVerifier {
     Bytes32 seed{};               // the batch's seed (every group's)
     Bytes32 partial{};            // the group's RLC partial (rlc only)
     int batch_ok = 0;
+    std::size_t pairs = 0;        // merged call (set_merge_groups): the Parameters groups it carries,
+                                  // cpz_verify_each_pairs_ex over `entries` entries; 0 otherwise
   };
 
   // Groups of at least this many entries take the RLC check (RLC_MIN_GROUP by default).
   void set_rlc_min_group(std::size_t m) { rlc_min_group_ = m; }
+  // Two or more groups below that threshold in one cpz_verify_each_pairs_ex call per
+  // CPZ_PAIRS_MAX groups instead of one cpz_verify_each_ex call each (off by default).
+  void set_merge_groups(bool on) { merge_groups_ = on; }
 
   // batch.rs:171-183.  `overall` is Err for an empty batch (and device failures); otherwise
   // the vector holds one Result per entry, in entry order.  `log` (optional) receives one
@@ -333,31 +342,23 @@ class BatchVerifier {
         if (i == 0) std::memcpy(seed.data(), draw, seed.size());
       }
     }
+    std::size_t small_groups = 0;
+    for (const auto& grp : groups) small_groups += grp.second.size() < rlc_min_group_ ? 1 : 0;
+    const bool merge = merge_groups_ && small_groups >= 2;
     uint64_t first_index = 0;
     for (const auto& grp : groups) {
       const auto& idx = grp.second;
       const std::size_t n = idx.size();
-      std::vector<uint8_t> y1(32 * n), y2(32 * n), r1(32 * n), r2(32 * n), s(32 * n), ctx_bytes, present(n), st(n);
-      std::vector<uint64_t> off(n + 1, 0);
-      bool any_ctx = false;
-      for (std::size_t k = 0; k < n; k++) {
-        const Entry& e = entries_[idx[k]];
-        std::memcpy(&y1[32 * k], e.statement.y1.data(), 32);
-        std::memcpy(&y2[32 * k], e.statement.y2.data(), 32);
-        std::memcpy(&r1[32 * k], e.proof.r1.data(), 32);
-        std::memcpy(&r2[32 * k], e.proof.r2.data(), 32);
-        std::memcpy(&s[32 * k], e.proof.s.data(), 32);
-        present[k] = e.context.has_value() ? 1 : 0;
-        if (e.context) {
-          any_ctx = true;
-          ctx_bytes.insert(ctx_bytes.end(), e.context->begin(), e.context->end());
-        }
-        off[k + 1] = ctx_bytes.size();
+      if (merge && n < rlc_min_group_) {  // issued below, with the other small groups
+        first_index += n;
+        continue;
       }
-      if (ctx_bytes.empty()) ctx_bytes.push_back(0);
-      const uint8_t* cb = any_ctx ? ctx_bytes.data() : nullptr;
-      const uint64_t* co = any_ctx ? off.data() : nullptr;
-      const uint8_t* cp = any_ctx ? present.data() : nullptr;
+      const Packed pk = pack(idx);
+      const std::vector<uint8_t>&y1 = pk.y1, &y2 = pk.y2, &r1 = pk.r1, &r2 = pk.r2, &s = pk.s;
+      std::vector<uint8_t> st(n);
+      const uint8_t* cb = pk.cb();
+      const uint64_t* co = pk.co();
+      const uint8_t* cp = pk.cp();
       const Parameters& p = grp.first;
       Dispatch d;
       d.entries = n;
@@ -381,6 +382,45 @@ class BatchVerifier {
       if (log) log->push_back(d);
       for (std::size_t k = 0; k < n; k++) out[idx[k]] = status_result(st[k]);
     }
+    if (merge) {
+      // the small groups, CPZ_PAIRS_MAX per call, each call's entries in batch order
+      std::size_t g0 = 0;
+      while (g0 < groups.size()) {
+        std::vector<uint8_t> gh;
+        std::vector<std::pair<std::size_t, uint32_t>> ent;  // (entry, pair of this call)
+        std::size_t g1 = g0;
+        for (; g1 < groups.size() && gh.size() < 64 * (std::size_t)CPZ_PAIRS_MAX; g1++) {
+          if (groups[g1].second.size() >= rlc_min_group_) continue;
+          const uint32_t pair = (uint32_t)(gh.size() / 64);
+          gh.insert(gh.end(), groups[g1].first.g.begin(), groups[g1].first.g.end());
+          gh.insert(gh.end(), groups[g1].first.h.begin(), groups[g1].first.h.end());
+          for (std::size_t i : groups[g1].second) ent.push_back({i, pair});
+        }
+        g0 = g1;
+        if (ent.empty()) continue;
+        std::sort(ent.begin(), ent.end());
+        std::vector<std::size_t> idx(ent.size());
+        std::vector<uint32_t> pair_idx(ent.size());
+        for (std::size_t k = 0; k < ent.size(); k++) {
+          idx[k] = ent[k].first;
+          pair_idx[k] = ent[k].second;
+        }
+        const Packed pk = pack(idx);
+        std::vector<uint8_t> st(idx.size());
+        Dispatch d;
+        d.entries = idx.size();
+        d.pairs = gh.size() / 64;
+        const int rc = cpz_verify_each_pairs_ex(dev_->get(), CPZ_CALL_EQUATIONS_ONLY, d.pairs, gh.data(), idx.size(),
+                                                pair_idx.data(), pk.y1.data(), pk.y2.data(), pk.r1.data(), pk.r2.data(),
+                                                pk.s.data(), pk.cb(), pk.co(), pk.cp(), st.data());
+        if (rc != CPZ_OK) {
+          if (overall) *overall = Result::err(ErrorKind::Device, cpz_last_error());
+          return {};
+        }
+        if (log) log->push_back(d);
+        for (std::size_t k = 0; k < idx.size(); k++) out[idx[k]] = status_result(st[k]);
+      }
+    }
     return out;
   }
 
@@ -391,9 +431,42 @@ class BatchVerifier {
     Proof proof;
     std::optional<std::vector<uint8_t>> context;
   };
+  // The rows and contexts of entries idx, as one call takes them.
+  struct Packed {
+    std::vector<uint8_t> y1, y2, r1, r2, s, ctx_bytes, present;
+    std::vector<uint64_t> off;
+    bool any_ctx = false;
+    const uint8_t* cb() const { return any_ctx ? ctx_bytes.data() : nullptr; }
+    const uint64_t* co() const { return any_ctx ? off.data() : nullptr; }
+    const uint8_t* cp() const { return any_ctx ? present.data() : nullptr; }
+  };
+  Packed pack(const std::vector<std::size_t>& idx) const {
+    const std::size_t n = idx.size();
+    Packed p;
+    for (std::vector<uint8_t>* v : {&p.y1, &p.y2, &p.r1, &p.r2, &p.s}) v->resize(32 * n);
+    p.present.resize(n);
+    p.off.assign(n + 1, 0);
+    for (std::size_t k = 0; k < n; k++) {
+      const Entry& e = entries_[idx[k]];
+      std::memcpy(&p.y1[32 * k], e.statement.y1.data(), 32);
+      std::memcpy(&p.y2[32 * k], e.statement.y2.data(), 32);
+      std::memcpy(&p.r1[32 * k], e.proof.r1.data(), 32);
+      std::memcpy(&p.r2[32 * k], e.proof.r2.data(), 32);
+      std::memcpy(&p.s[32 * k], e.proof.s.data(), 32);
+      p.present[k] = e.context.has_value() ? 1 : 0;
+      if (e.context) {
+        p.any_ctx = true;
+        p.ctx_bytes.insert(p.ctx_bytes.end(), e.context->begin(), e.context->end());
+      }
+      p.off[k + 1] = p.ctx_bytes.size();
+    }
+    if (p.ctx_bytes.empty()) p.ctx_bytes.push_back(0);
+    return p;
+  }
   Device* dev_;
   std::vector<Entry> entries_;
   std::size_t rlc_min_group_ = RLC_MIN_GROUP;
+  bool merge_groups_ = false;
 };
 
 }  // namespace chaum_pedersen

@@ -221,6 +221,34 @@ impl Gpu {
         Ok(st)
     }
 
+    /// Entries that carry their own generators, in one call and one verify launch
+    /// (`cpz_verify_each_pairs_ex`): entry i is verified under `pairs[pair_idx[i]]` (g, h), at most
+    /// `CPZ_PAIRS_MAX` pairs and `CPZ_PAIRS_MAX_PROOFS` entries; each status is what
+    /// `verify_each_with` returns for that entry under its own pair.
+    pub fn verify_each_pairs(&self, flags: CallFlags, pairs: &[(Bytes32, Bytes32)], pair_idx: &[u32],
+                             entries: &[Entry<'_>]) -> Result<Vec<u8>, GpuError> {
+        if pair_idx.len() != entries.len() {
+            return Err(GpuError { code: sys::CPZ_EINVAL, message: "pair_idx must hold one index per entry".into() });
+        }
+        let mut gh = Vec::with_capacity(64 * pairs.len());
+        for (g, h) in pairs {
+            gh.extend_from_slice(g);
+            gh.extend_from_slice(h);
+        }
+        let soa = Soa::new(entries);
+        let (cb, co, cp) = soa.ctx_ptrs();
+        let mut st = vec![0u8; entries.len()];
+        let r = &soa.rows;
+        // SAFETY: gh holds 64 * pairs.len() bytes, pair_idx n indices (checked by the library before
+        // any use), every row 32 * n bytes; contexts hold n + 1 offsets / n flags.
+        check(unsafe {
+            sys::cpz_verify_each_pairs_ex(self.ctx, flags, pairs.len(), gh.as_ptr(), entries.len(), pair_idx.as_ptr(),
+                                          r[0].as_ptr(), r[1].as_ptr(), r[2].as_ptr(), r[3].as_ptr(), r[4].as_ptr(),
+                                          cb, co, cp, st.as_mut_ptr())
+        })?;
+        Ok(st)
+    }
+
     /// `Verifier::verify_response` (verifier/mod.rs:144-171) with caller challenges.
     pub fn verify_response(&self, g: &Bytes32, h: &Bytes32, entries: &[Entry<'_>], challenges: &[Bytes32])
                            -> Result<Vec<u8>, GpuError> {
