@@ -4,6 +4,9 @@
                            (hipcc --offload-arch=gfx950).
 * ``tests/native/libcpz_hosttest.so`` -- CPU build of the device-library headers with
                            limb-bound assertions, for unit tests only.
+* ``tests/native/libcpz_devprobe.so`` -- gfx950 build of the device-only headers (fe16.h,
+                           keccak_wave.h, the device arm of the challenge split) behind plain C
+                           probes, for the GPU unit tests only; never linked into the product.
 * ``oracle/``            -- delegated to oracle/Makefile (the C oracle: CPU baseline and
                            at-scale checker; test infrastructure only).
 
@@ -23,6 +26,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIBCPZ = os.path.join(LIBDIR, "libcpz.so")
 HOSTTEST = os.path.join(ROOT, "tests", "native", "libcpz_hosttest.so")
+DEVPROBE = os.path.join(ROOT, "tests", "native", "libcpz_devprobe.so")
 ARCH = os.environ.get("CPZ_OFFLOAD_ARCH", "gfx950")
 
 
@@ -115,6 +119,21 @@ def build_hosttest(force: bool = False) -> str:
     return HOSTTEST
 
 
+def build_devprobe(force: bool = False, out: str = DEVPROBE, include: str = CSRC) -> str:
+    """Device probes over the product headers (tests/native/devprobe.hip), compiled like the
+    product's units.  `out` / `include` build the probes over another copy of the headers
+    (a mutated one, or an earlier commit's) for tests/test_gpu_row_arith.py's CPZ_DEVPROBE."""
+    src = os.path.join(ROOT, "tests", "native", "devprobe.hip")
+    hdrs = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h")]
+    if not force and not _newer(out, [src] + hdrs):
+        return out
+    tmp = out + ".tmp"
+    _run([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", include,
+          "-I", os.path.join(ROOT, "include"), "-shared", src, "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 CPP_TEST = os.path.join(ROOT, "tests", "cpp", "batch_verifier_test")
 
 
@@ -175,6 +194,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_hosttest(force)
     build_oracle(force)
     build_libcpz(force, verbose)
+    build_devprobe(force)
     build_cpp_test(force)
     build_dropin_test(force)
     build_merge_groups_test(force)

@@ -28,8 +28,12 @@
 // A doubling or an addition is two stages (dalek's ProjectivePoint::double and
 // EdwardsPoint + ProjectiveNielsPoint, through CompletedPoint -> extended).
 //
-// Device-only (DPP, permlane); the CPU never runs it: parity is k_verify_wide's statuses
-// against the oracle (tests/test_gpu_scale.py), like every other kernel's.
+// Device-only (DPP, permlane); the CPU never runs it.  Parity: tests/native/devprobe.hip runs
+// each operation here on its own and tests/test_gpu_row_arith.py compares the raw limbs, words
+// and flags with big integers and the oracle, at the operand bounds above and at the field's
+// edge values; tests/row_model.py is the same algorithm in plain Python with these bounds as
+// assertions (tests/test_row_model.py), limb-for-limb equal to the device's mul / mul_pair.
+// k_verify_wide's statuses against the oracle (tests/test_gpu_scale.py) cover the composition.
 #pragma once
 #include <stdint.h>
 
@@ -228,7 +232,10 @@ __device__ __forceinline__ void to_words(uint32_t out[8], int x) {
   uint32_t x8[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) x8[i] = h[2 * i] | (h[2 * i + 1] << 16);
-  // [0, 2^256) -> [0, p): subtract p up to twice (x >= p iff x + 19 >= 2^255)
+  // [0, 2^256) -> [0, p): subtract p up to twice (x >= p iff x + 19 >= 2^255).  x - p is
+  // x + 19 - 2^255: bit 255 of the sum is cleared -- unless the sum carried out of 256 bits
+  // (x >= 2^256 - 19: a product may hold the field values 19..37 as 2p + j), where the
+  // difference is y + 2^255 and the bit stays for the second pass to take off.
 #pragma unroll
   for (int rep = 0; rep < 2; rep++) {
     uint64_t cc = 19;
@@ -240,7 +247,7 @@ __device__ __forceinline__ void to_words(uint32_t out[8], int x) {
       cc >>= 32;
     }
     const bool ge = (y[7] >> 31) != 0 || cc != 0;
-    y[7] &= 0x7fffffffu;
+    y[7] = cc != 0 ? (y[7] | 0x80000000u) : (y[7] & 0x7fffffffu);
 #pragma unroll
     for (int i = 0; i < 8; i++) x8[i] = ge ? y[i] : x8[i];
   }

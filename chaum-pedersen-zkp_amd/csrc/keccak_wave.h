@@ -1,8 +1,10 @@
 // Keccak-f[1600] spread over the lanes of one wave (k_verify_wide's wave 4, which computes
 // ONE transcript challenge per workgroup).  Replaces, for that wave, the register form of
 // transcript.h keccak_f1600 (the permutation of STROBE-128 under merlin, transcript.rs:29-71).
-// Device-only; parity: tools/ubench/w4_parts.hip checks it against the register form, and
-// k_verify_wide's challenges are compared with the oracle's in tests/test_gpu_scale.py.
+// Device-only; parity: tests/test_gpu_row_arith.py runs PermRows alone (tests/native/devprobe.hip)
+// against the oracle's Keccak-f[1600] on zero, all-ones and random states; tools/ubench/w4_parts.hip
+// checks it against the register form, and k_verify_wide's challenges are compared with the
+// oracle's in tests/test_gpu_scale.py.
 #pragma once
 #include <stdint.h>
 

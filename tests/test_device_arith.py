@@ -11,6 +11,7 @@ import random
 import pytest
 
 import pyoracle as O
+from split_cases import euclid_half, half_split_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, L = O.P, O.L
@@ -188,38 +189,18 @@ def test_golden_proofs_host_build(lib, golden):
         assert lib.cpzt_verify(g, h, f["y1"], f["y2"], f["r1"], f["r2"], f["s"], cb, len(cb), 1) == 1
 
 
-def _euclid_half(c):
-    """Exact partial extended Euclid on (l, c): first remainder below 3 * 2^125."""
-    T = 3 << 125
-    r0, r1, t0, t1 = L, c, 0, 1
-    while r1 >= T:
-        q = r0 // r1
-        r0, r1 = r1, r0 - q * r1
-        t0, t1 = t1, t0 - q * t1
-    return r1, t1
-
-
 @pytest.mark.parametrize("fn", ["cpzt_half_split", "cpzt_half_split32"])
 def test_half_split(lib, fn):
     """sc_half_split (csrc/scalar25519.h): v c = u (mod l), u, |v| < 3 * 2^125, and equal
     to the exact Euclid values -- incl. huge partial quotients (the shifted-divisor path) --
     with 63-bit Lehmer windows and f64 quotients, and with k_verify_wide's 31-bit windows."""
-    rng = random.Random(7)
-    cases = [0, 1, 2, (3 << 125) - 1, 3 << 125, L - 1, L - 2, L // 2, L // 3, (L >> 70), (L >> 140) + 5,
-             (L >> 126), (L >> 127) + 1, 2**252, (2**128 + 1) % L]
-    cases += [rng.randrange(L) for _ in range(20000)]
-    # Values near rationals p/q of l: a few tiny-then-huge partial quotients, which stress
-    # the Lehmer batch's exactness conditions and the huge-quotient single steps.
-    for q in (2, 3, 5, 7, 1000, 65537, 2**31 - 1, 2**40 + 3, 2**64 + 13, 2**100 + 7):
-        for p in (1, q // 2 + 1, q - 1):
-            base = L * p // q
-            cases += [(base + d) % L for d in (-2, -1, 0, 1, 2, 1 << 20, rng.randrange(1 << 60))]
+    cases = half_split_cases()  # tests/split_cases.py: the device tests run the same list
     u, v, neg = buf(16), buf(16), ctypes.c_int()
     for c in cases:
         getattr(lib, fn)(u, v, ctypes.byref(neg), c.to_bytes(32, "little"))
         uu = fi(u.raw)
         vv = -fi(v.raw) if neg.value else fi(v.raw)
-        assert (uu, vv) == _euclid_half(c), c
+        assert (uu, vv) == euclid_half(c), c
         assert vv != 0 and (vv * c - uu) % L == 0
         assert uu < 3 << 125 and abs(vv) < 3 << 125
 
