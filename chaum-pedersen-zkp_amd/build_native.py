@@ -106,15 +106,15 @@ def build_clock_probe(force: bool = False) -> str:
 
 
 def build_hosttest(force: bool = False) -> str:
-    src = os.path.join(ROOT, "tests", "native", "hostlib.cpp")
-    if not force and not _newer(HOSTTEST, [src] + _headers()):
+    srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("hostlib.cpp", "hostlib_joint.cpp")]
+    if not force and not _newer(HOSTTEST, srcs + _headers()):
         return HOSTTEST
     cxx = shutil.which("g++") or "g++"
     tmp = HOSTTEST + ".tmp"
     # CPZ_HOST_DEFINES: extra -D flags to check a tuning variant of the device library on the CPU
     extra = ["-D" + d for d in os.environ.get("CPZ_HOST_DEFINES", "").split()]
     _run([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-DCPZ_BOUNDS_CHECK", "-DCPZ_COUNT_OPS"] + extra +
-         ["-I", CSRC, src, "-o", tmp])
+         ["-I", CSRC] + srcs + ["-o", tmp])
     os.replace(tmp, HOSTTEST)
     return HOSTTEST
 

@@ -30,7 +30,7 @@ constexpr bool niels_parts_consistent() {
   return true;
 }
 static_assert(niels_parts_consistent(), "kNielsLevelOfPart must invert niels_level_doublings");
-constexpr int kCachedEntries = 2 * kTableSlots;   // y and r tables (identity + 1..8): |d| <= 8
+constexpr int kCachedEntries = kJointSlots;   // one equation's joint table (scalarmul.h), per thread
 #ifndef CPZ_VERIFY_BLOCK
 #define CPZ_VERIFY_BLOCK 256
 #endif
@@ -132,6 +132,13 @@ constexpr int kQuadPhases = 9;
 // barrier B, verdict; wave 2 digits, [s'] B; 100 MHz at wave 0's start / end; wave 2's start.
 constexpr int kSmallStamps = 16;
 constexpr int64_t kQuadProofScratch = 2 * kQuadTableInts * 4;
+// Bytes of slab per k_verify_each thread.  The slab is sized by the eight-lane kernel, whose
+// bound (verify_quad_max) is the proofs one slab holds: kVerifyBlock / 2 proofs per block of the
+// per-proof grid.  The per-proof kernels' own tables (kCachedEntries entries per thread, packed
+// from the slab's start) take less, so they touch only the first 13/18 of it.
+constexpr int64_t kSlabThreadBytes =
+    kQuadProofScratch / 2 > (int64_t)(kCachedEntries * sizeof(ge_cached)) ? kQuadProofScratch / 2
+                                                                          : (int64_t)(kCachedEntries * sizeof(ge_cached));
 
 struct VerifyArgs {
   int64_t n;
@@ -143,7 +150,7 @@ struct VerifyArgs {
   const uint32_t* c;
   uint8_t* status;               // in: response-scalar status; out: final status
   const ge_niels* comb;          // fixed-base combs of g then h, kCombPerBase entries each
-  char* scratch;                 // table slab: grid * kVerifyBlock threads x kCachedEntries ge_cached
+  char* scratch;                 // table slab: grid * kVerifyBlock threads x kSlabThreadBytes
   const ge_niels* pre = nullptr; // RLC fallback: the prepared Niels points (-r1, -y1, -r2, -y2 of
                                  // proof i at 4 i ..), reused instead of decoding; entries whose
                                  // decode-level status is non-zero keep it

@@ -13,9 +13,10 @@
 //   k_verify_each        1 thread / proof: challenge split v c = u (mod l) with
 //                        u, |v| < 2^127 (verify.h), 4 ristretto decodes, then per equation
 //                        [v s] B - [u] y - [v] r in E[4]  <=>  [s] B - [c] y == r
-//                        by a half-length Straus loop: radix-16 signed digits of u and |v|
-//                        against per-proof tables of 8 multiples of -y and -+r (HBM-backed
-//                        scratch), then [v s mod l] B as 16 mixed additions from the
+//                        by a half-length joint Straus loop: radix-4 signed digits of u and |v|
+//                        against one per-proof table of the 13 combinations a (-y) + b (-+r),
+//                        a in 0..2, b in -2..2 (HBM-backed scratch), then [v s mod l] B as 16
+//                        mixed additions from the
 //                        fixed-base comb of B in HBM (radix-2^16 digits).
 //                        batch.rs:185-231, verifier/mod.rs:144-171
 //   k_parse_proofs       bulk Proof::from_bytes (gadgets.rs:364-489) into SoA rows + codes

@@ -221,7 +221,7 @@ struct cpz_ctx {
   // work buffers
   DevBuf c;         // n x 32
   DevBuf st;        // n
-  DevBuf scratch;   // per-stream table slabs (kCachedEntries ge_cached per thread)
+  DevBuf scratch;   // per-stream table slabs (kSlabThreadBytes per thread)
   // host-API staging (y1, y2, r1, r2, s, and challenges / witnesses / nonces)
   DevBuf in[7];
   DevBuf ctxb, ctxo, ctxp;
@@ -542,7 +542,7 @@ int verify_full_grid(const cpz_ctx* ctx) {
   return (occupancy_grid(ctx) + CPZ_VERIFY_CHUNK_DIV - 1) / CPZ_VERIFY_CHUNK_DIV;
 }
 size_t verify_slab_bytes(const cpz_ctx* ctx) {
-  return (size_t)verify_full_grid(ctx) * cpz::kVerifyBlock * cpz::kCachedEntries * sizeof(cpz::ge_cached);
+  return (size_t)verify_full_grid(ctx) * cpz::kVerifyBlock * (size_t)cpz::kSlabThreadBytes;
 }
 // Launches of at most this many proofs take the eight-lane kernel (k_verify_quad): kQuadVerifyMax,
 // bounded by the tables one slab holds -- full * 128 proofs, which depends on the device's CUs

@@ -608,4 +608,37 @@ CPZ_HD void sc_recode_radix16_half(uint32_t out[4], const uint32_t s[4]) {
   }
 }
 
+// Signed radix-4 recoding of a value < 3 * 2^125 held in 4 words (u or |v| of sc_half_split):
+// 64 digits, digit i in bits 2 (i % 16) of word i / 16.  Digits 0..62 are in [-2, 1], packed as
+// 2-bit two's complement; digit 63 is UNSIGNED, in 0..2.
+//
+// Carry bound: a digit is n = bits + carry in 0..4 and carries (n + 2) >> 2 <= 1.  The value is
+// below 2^126 + 2^125, so bits 126..127 are 0 or 1, and when they are 1 bit 125 is clear: digit
+// 62 then sees bits <= 1, n <= 2.  The top digit is at most 1 + 1 = 2, with no carry out.
+CPZ_HD void sc_recode_radix4_half(uint32_t out[4], const uint32_t s[4]) {
+  CPZ_ASSERT(s[3] < 0x60000000u);
+  int32_t carry = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    uint32_t packed = 0;
+#pragma unroll
+    for (int m = 0; m < 16; m++) {
+      const int32_t n = (int32_t)((s[j] >> (2 * m)) & 3u) + carry;
+      if (j == 3 && m == 15) {
+        CPZ_ASSERT(n <= 2);
+        carry = 0;
+        packed |= (uint32_t)n << 30;
+      } else {
+        carry = (n + 2) >> 2;
+        packed |= ((uint32_t)(n - (carry << 2)) & 3u) << (2 * m);
+      }
+    }
+    out[j] = packed;
+  }
+}
+
+// Digit i of such a recoding (word w = the word holding it, m = i % 16): signed for i < 63.
+CPZ_HD int radix4_digit(uint32_t w, int m) { return ((int32_t)(w << (30 - 2 * m))) >> 30; }
+CPZ_HD int radix4_top_digit(uint32_t w3) { return (int)(w3 >> 30); }
+
 }  // namespace cpz

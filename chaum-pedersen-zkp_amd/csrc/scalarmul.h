@@ -10,6 +10,7 @@
 #pragma once
 #include "timing_only.h"
 #include "ristretto.h"
+#include "scalar25519.h"
 
 namespace cpz {
 
@@ -211,34 +212,99 @@ CPZ_HD ge_p1p1 comb_add(ge_p1p1 cur, const Comb& comb, const Dig& sd) {
   return cur;
 }
 
+// Joint table of one equation (see verify.h): the 13 cached combinations a Y' + b R' with
+// a in 0..2, b in -2..2 at slot 5 a + b, slot 0 the identity.  A window's signed digit pair
+// (a, b) is the entry |5 a + b|, negated when 5 a + b < 0 (|b| <= 2 < 5: that is a < 0, or a = 0
+// and b < 0).
+constexpr int kJointSlots = 13;
+CPZ_HD constexpr int joint_slot(int a, int b) { return 5 * a + b; }
+// Signed slot of window m < 16 of a digit-word pair (wu, wv), and the top window's (unsigned).
+CPZ_HD int joint_window(uint32_t wu, uint32_t wv, int m) { return joint_slot(radix4_digit(wu, m), radix4_digit(wv, m)); }
+CPZ_HD int joint_top_window(uint32_t wu3, uint32_t wv3) {
+  return joint_slot(radix4_top_digit(wu3), radix4_top_digit(wv3));
+}
+
+// Writes the joint table of AFFINE Y, R (Z = 1, as decoded): 70 M + 16 S, 13 stores.
+//   (1, 0), (0, 1)   the points themselves, their 2 d T one product each;
+//   (1, s)           Y + s R, a mixed addition (s = +1, -1);
+//   (1, 2 s)         (1, s) + s R;
+//   (2, s)           (1, s) + Y;
+//   (2, 2 s)         2 (1, s);
+//   (2, 0), (0, 2)   2 Y, 2 R.
+// One copy of the addition code (the rolled loops over s and j) and one of the doubling code
+// (the loop over d); beside the two affine inputs at most two extended points are live: (1, s)
+// and the one being stored.  (The compiler spills in this function, not in the Straus loop.)
+CPZ_HD void build_joint_table(const SlabTable& tab, const ge_p3& Y, const ge_p3& R) {
+  ge_niels nY, nR;
+  nY.ypx = fe_add(Y.Y, Y.X);
+  nY.ymx = fe_sub(Y.Y, Y.X);
+  nY.xy2d = fe_mul(Y.T, FE_D2());
+  nR.ypx = fe_add(R.Y, R.X);
+  nR.ymx = fe_sub(R.Y, R.X);
+  nR.xy2d = fe_mul(R.T, FE_D2());
+  tab.store(0, ge_cached_identity());
+  tab.store(joint_slot(1, 0), ge_cached{nY.ypx, nY.ymx, Y.Z, nY.xy2d});
+  tab.store(joint_slot(0, 1), ge_cached{nR.ypx, nR.ymx, R.Z, nR.xy2d});
+#pragma unroll 1
+  for (int neg = 0; neg < 2; neg++) {
+    const int s = neg ? -1 : 1;
+    const ge_niels nRs = ge_niels_cneg(nR, neg != 0);
+    ge_p3 A = Y;
+#pragma unroll 1
+    for (int j = 0; j < 3; j++) {
+      // j = 0: Y + s R = (1, s), kept in A;  j = 1: A + s R = (1, 2 s);  j = 2: A + Y = (2, s)
+      const ge_p3 Q = p1p1_to_p3(ge_add_niels(A, j == 2 ? nY : nRs));
+      tab.store(j == 0 ? joint_slot(1, s) : (j == 1 ? joint_slot(1, 2 * s) : joint_slot(2, s)), p3_to_cached(Q));
+      if (j == 0) A = Q;
+    }
+#pragma unroll 1
+    for (int d = 0; d < 2; d++) {
+      // d = 0: 2 A = (2, 2 s);  d = 1: 2 Y = (2, 0) in the first pass over s, 2 R = (0, 2) in the second
+      const ge_p3& P = d == 0 ? A : (neg ? R : Y);
+      const int slot = d == 0 ? joint_slot(2, 2 * s) : (neg ? joint_slot(0, 2) : joint_slot(2, 0));
+      tab.store(slot, p3_to_cached(p1p1_to_p3(p2_dbl(ge_p2{P.X, P.Y, P.Z}))));
+    }
+  }
+}
+
+// The completed form ((X:Z), (Y:T)) of a cached entry: x = (YpX - YmX) / 2Z, y = (YpX + YmX) / 2Z.
+// No product, and the limbs are exactly 2 X, 2 Y, 2 Z of the tight point the entry was made from.
+CPZ_HD ge_p1p1 cached_to_p1p1(const ge_cached& e) {
+  ge_p1p1 r;
+  r.X = fe_sub(e.YpX, e.YmX);
+  r.Y = fe_add(e.YpX, e.YmX);
+  r.Z = fe_add(e.Z, e.Z);
+  r.T = r.Z;
+  return r;
+}
+
 // Half-size per-proof check with the comb (see verify.h):
-//   Q = [u] Y' + [v] R' (Straus, 31 x 4 doublings, 64 cached additions) + [s'] B (comb),
+//   Q = [u] Y' + [v] R' (joint Straus: 63 x 2 doublings, 63 cached additions) + [s'] B (comb),
 // returned as a completed point (callers only test it for the identity).
-// tab_y / tab_r: cached multiples 1..8 of Y' / R'; udig, vdig: 32 radix-16 signed digits of
-// u, |v| < 6 * 2^124; sdig: 16 radix-2^16 signed digits of s' < 2^253.
+// tab: the joint table of Y', R'; ud, vd: the radix-4 digits of u, |v| < 3 * 2^125
+// (sc_recode_radix4_half); sdig: 16 radix-2^16 signed digits of s' < 2^253.
+// The top window (unsigned digits, nothing to double yet) starts the sum from its entry in
+// completed form, which the next window's doublings take as it is.
 template <class Comb, class Dig>
-CPZ_HD ge_p1p1 straus_half_comb(const SlabTable& tab_y, const SlabTable& tab_r, const Comb& comb, const Dig& ud,
-                              const Dig& vd, const Dig& sdig) {
-  ge_p1p1 cur = p1p1_identity();
+CPZ_HD ge_p1p1 straus_half_joint(const SlabTable& tab, const Comb& comb, const Dig& ud, const Dig& vd,
+                                 const Dig& sdig) {
+  ge_p1p1 cur = cached_to_p1p1(tab.load(joint_top_window(ud[3], vd[3])));
 #pragma unroll 1
   for (int j = 3; j >= 0; j--) {
     const uint32_t wu = ud[j], wv = vd[j];
 #pragma unroll 1
-    for (int m = 7; m >= 0; m--) {
-      const int du = ((int32_t)(wu << (28 - 4 * m))) >> 28;
-      const int dv = ((int32_t)(wv << (28 - 4 * m))) >> 28;
-      // both table loads issued before the four doublings, which hide their latency
-      // (the tables live in the HBM-backed scratch slab; measured ~1 % faster)
-      const ge_cached ey = cached_lookup(tab_y, du), er = cached_lookup(tab_r, dv);
-      if (j != 3 || m != 7) cur = dbl4(cur);
+    for (int m = j == 3 ? 14 : 15; m >= 0; m--) {
+      // the table load issued before the two doublings, which hide part of its latency
+      // (the table lives in the HBM-backed scratch slab)
+      const ge_cached e = cached_lookup(tab, joint_window(wu, wv, m));
+      cur = p2_dbl(p1p1_to_p2(cur));
+      cur = p2_dbl(p1p1_to_p2(cur));
 #if defined(CPZ_EXP_NIELS_TABLES)
-      // timing experiment only (timing_only.h: wrong verdicts): the entries added as affine
-      // Niels points, Z never read -- the best case of normalised per-proof tables
-      cur = ge_add_niels(p1p1_to_p3(cur), ge_niels{ey.YpX, ey.YmX, ey.T2d, {0, 0}});
-      cur = ge_add_niels(p1p1_to_p3(cur), ge_niels{er.YpX, er.YmX, er.T2d, {0, 0}});
+      // timing experiment only (timing_only.h: wrong verdicts): the entry added as an affine
+      // Niels point, Z never read -- the best case of normalised per-proof tables
+      cur = ge_add_niels(p1p1_to_p3(cur), ge_niels{e.YpX, e.YmX, e.T2d, {0, 0}});
 #else
-      cur = ge_add_cached(p1p1_to_p3(cur), ey);
-      cur = ge_add_cached(p1p1_to_p3(cur), er);
+      cur = ge_add_cached(p1p1_to_p3(cur), e);
 #endif
     }
   }

@@ -275,10 +275,12 @@ CPZ_HD ge_niels niels_load(const ge_niels* p) {
 template <bool kPre, class Comb, class Dig>
 CPZ_HD bool check_equation(const Dig& y, const Dig& r, const ge_niels* pre_y, const ge_niels* pre_r,
                            const Dig& udig, const Dig& vdig, bool vneg, const Dig& sdig, const Comb& comb,
-                           const SlabTable& tab_y, const SlabTable& tab_r, bool& decoded, bool& r_identity) {
-  // One copy of the decode + table code for both points (a rolled loop): the kernel's
-  // instruction footprint, not its arithmetic, is what the 64 KB instruction cache sees.
+                           const SlabTable& tab, bool& decoded, bool& r_identity) {
+  // One copy of the decode code for both points (a rolled loop): the kernel's instruction
+  // footprint, not its arithmetic, is what the 64 KB instruction cache sees.  Then one joint
+  // table of Y' = -Y and R' = -R (R when v < 0: the digits are those of |v|).
   decoded = true;
+  ge_p3 Yp, Rp;
 CPZ_EQ_LOOP
   for (int k = 0; k < 2; k++) {
     ge_p3 P;
@@ -290,8 +292,10 @@ CPZ_EQ_LOOP
       for (int q = 0; q < 8; q++) w[q] = k ? r[q] : y[q];
       decoded = ristretto_decode(P, w) && decoded;
     }
-    build_cached_table(k ? tab_r : tab_y, (k && vneg) ? P : ge_neg(P));
+    P = (k && vneg) ? P : ge_neg(P);
+    if (k) Rp = P; else Yp = P;
   }
+  build_joint_table(tab, Yp, Rp);
   if constexpr (kPre) {
     r_identity = false;
   } else {
@@ -302,18 +306,18 @@ CPZ_EQ_LOOP
   }
 #if defined(CPZ_EXP_EXTRA_INV)
   // timing experiment only (timing_only.h: wrong verdicts): one field inversion per equation
-  ge_p1p1 q = straus_half_comb(tab_y, tab_r, comb, udig, vdig, sdig);
+  ge_p1p1 q = straus_half_joint(tab, comb, udig, vdig, sdig);
   q.X = fe_mul(q.X, fe_invert(q.Z));
   return ristretto_is_identity(q);
 #else
-  return ristretto_is_identity(straus_half_comb(tab_y, tab_r, comb, udig, vdig, sdig));
+  return ristretto_is_identity(straus_half_joint(tab, comb, udig, vdig, sdig));
 #endif
 }
 
 // Full per-proof outcome given the challenge c (canonical) and the response status st_s.
-// comb_g / comb_h: fixed-base combs of g and h; tab_v: 2 * kTableSlots entries of per-proof
-// scratch (the y table, then the r table); dig: 16 words of digit storage at stride dstride
-// (u: words 0-3, |v|: 4-7, v s mod l: 8-15).
+// comb_g / comb_h: fixed-base combs of g and h; tab_v: kJointSlots entries of per-proof
+// scratch (the joint table of one equation, rebuilt for the second); dig: 16 words of digit
+// storage at stride dstride (u: words 0-3 and |v|: 4-7 in radix 4, v s mod l: 8-15).
 // rows: the encodings y1, y2, r1, r2 (words at rows[4 q + ...], see DigitRef: the verify kernel
 // stages them in LDS so that no per-row address stays live in registers); pre (kPre only):
 // the entry's 4 prepared Niels points (-r1, -y1, -r2, -y2), st_s its decode-level status,
@@ -331,7 +335,7 @@ CPZ_HD uint8_t verify_proof(const DigitRef& y1, const DigitRef& y2, const DigitR
   // recodings skipped
   vneg = c[7] & 1;
   for (int k = 0; k < 8; k++) {
-    dig[k * dstride] = c[k];
+    dig[k * dstride] = k % 4 == 3 ? c[k] & 0x3fffffffu : c[k];  // top digits 0: every slot inside the table
     dig[(8 + k) * dstride] = s[k];
   }
   if (0)
@@ -339,8 +343,8 @@ CPZ_HD uint8_t verify_proof(const DigitRef& y1, const DigitRef& y2, const DigitR
   {
     uint32_t u[4], va[4], w[8];
     sc_half_split(c, u, va, vneg);
-    sc_recode_radix16_half(w, u);
-    sc_recode_radix16_half(w + 4, va);
+    sc_recode_radix4_half(w, u);
+    sc_recode_radix4_half(w + 4, va);
     for (int k = 0; k < 8; k++) dig[k * dstride] = w[k];
     sc vs, ss;
 #pragma unroll
@@ -360,8 +364,7 @@ CPZ_EQ_LOOP
   for (int e = 0; e < 2; e++) {
     bool d, r_id;
     eq = check_equation<kPre>(e ? y2 : y1, e ? r2 : r1, kPre ? pre + 1 + 2 * e : nullptr, kPre ? pre + 2 * e : nullptr,
-                              udig, vdig, vneg, sdig, e ? comb_h : comb_g, tab_v, tab_v.shifted(kTableSlots), d,
-                              r_id) && eq;
+                              udig, vdig, vneg, sdig, e ? comb_h : comb_g, tab_v, d, r_id) && eq;
     dec = dec && d;
     id = id || r_id;
   }

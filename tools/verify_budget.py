@@ -4,10 +4,10 @@
 
 k.s is the device assembly of kernels.hip (built here with the product flags when omitted).  The
 loops are found by their MAD counts, which follow from the formulas (tools/isa_hist.py prints every
-loop): the Straus step's additions (2 cached additions, each p1p1->p3 + add: 16 products x 110
-MADs = 1760), one doubling of the 4 per window (p1p1->p2 + 4 squarings: 3 x 110 + 4 x 65 = 590,
-one MAD of which is address arithmetic), the comb's mixed addition (7 x 110 = 770) and one squaring
-of the decode chains (55).  Each class is priced at the issue cost the clock_rates sweep measured for
+loop): the joint Straus loop's radix-4 window (2 doublings, each p1p1->p2 + 4 squarings: 3 x 110 +
+4 x 65 = 590, one MAD of which is address arithmetic, and one cached addition, p1p1->p3 + add: 8
+products x 110 MADs = 880; 2058 in one loop body), the comb's mixed addition (7 x 110 = 770) and one
+squaring of the decode chains (55).  Each class is priced at the issue cost the clock_rates sweep measured for
 its representative instruction at 2 waves/SIMD (the kernel's occupancy), in SIMD cycles per wave64
 instruction; scalar instructions issue on the scalar unit and are priced at 0.
 """
@@ -37,7 +37,7 @@ CLASSES = [  # (class, mnemonic prefixes, clock_rates op that prices it)
     ("memory: global / ds loads", ("global_", "ds_", "scratch_", "buffer_"), None),
     ("scalar + control (s_*)", ("s_",), None),
 ]
-LOOPS = [("straus_additions", 1760), ("doubling", 589), ("comb_mixed_addition", 770), ("decode_squaring", 55)]
+LOOPS = [("straus_window", 2058), ("comb_mixed_addition", 770), ("decode_squaring", 55)]
 
 
 def classify(mn):
@@ -84,21 +84,9 @@ def main():
             e["cycles"] = round(e["cycles"], 1)
         out["loops"][name] = {"instructions": tot_i, "cycles": round(tot_c, 1),
                               "classes": dict(sorted(per.items(), key=lambda kv: -kv[1]["cycles"]))}
-    win = [out["loops"].get("straus_additions"), out["loops"].get("doubling")]
-    if all(win):
-        agg = collections.defaultdict(lambda: {"instructions": 0, "cycles": 0.0})
-        for mult, lp in ((1, win[0]), (4, win[1])):
-            for cls, e in lp["classes"].items():
-                agg[cls]["instructions"] += mult * e["instructions"]
-                agg[cls]["cycles"] += mult * e["cycles"]
-        ti = sum(e["instructions"] for e in agg.values())
-        tc = sum(e["cycles"] for e in agg.values())
-        out["straus_window"] = {
-            "what": "one radix-16 window of the two-point Straus loop: 4 doublings + 2 cached additions",
-            "instructions": ti, "cycles": round(tc, 1),
-            "classes": {k: {"instructions": v["instructions"], "share_instructions": round(v["instructions"] / ti, 4),
-                            "cycles": round(v["cycles"], 1), "share_cycles": round(v["cycles"] / tc, 4)}
-                        for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["cycles"])}}
+    if out["loops"].get("straus_window"):
+        out["loops"]["straus_window"]["what"] = ("one radix-4 window of the joint Straus loop: 2 doublings + 1 cached "
+                                                 "addition")
     json.dump(out, sys.stdout, indent=1)
     print()
 
