@@ -399,6 +399,13 @@ int cpzt_challenge_ctx32(uint8_t* out, const uint8_t* g, const uint8_t* h, const
   return 0;
 }
 
+// The packed signed digits of the response recodings (tests/digit_vectors.py models them):
+// s < 2^253 in 8 words for radix 2^16 and 2^8, a value below 6 * 2^124 in 4 words for the
+// half-size radix 16.
+void cpzt_recode_radix65536(uint32_t out[8], const uint32_t in[8]) { sc_recode_radix65536(out, in); }
+void cpzt_recode_radix256(uint32_t out[8], const uint32_t in[8]) { sc_recode_radix256(out, in); }
+void cpzt_recode_radix16_half(uint32_t out[4], const uint32_t in[4]) { sc_recode_radix16_half(out, in); }
+
 // Half-size challenge split: u, |v| (16 bytes each, little-endian), sign of v.
 void cpzt_half_split(uint8_t* u_out, uint8_t* v_out, int* vneg, const uint8_t* c) {
   uint32_t cw[8], u[4], v[4];

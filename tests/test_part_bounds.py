@@ -13,19 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 import pyoracle as O  # noqa: E402
+from digit_vectors import recode16  # noqa: E402  (rlc_dev.h recode16 = sc_recode_radix65536)
 
 TOP_BUCKETS = 16  # kPartTopBuckets
-
-
-def recode16(s):
-    """rlc_dev.h recode16: 16 signed radix-2^16 digits of s < 2^253."""
-    d, carry = [], 0
-    for w in range(16):
-        chunk = ((s >> (16 * w)) & 0xFFFF) + carry
-        carry = (chunk + 0x8000) >> 16
-        d.append(chunk - (carry << 16))
-    assert carry == 0
-    return d
 
 
 def split8(d):
