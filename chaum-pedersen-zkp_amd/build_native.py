@@ -7,6 +7,9 @@
 * ``tests/native/libcpz_devprobe.so`` -- gfx950 build of the device-only headers (fe16.h,
                            keccak_wave.h, the device arm of the challenge split) behind plain C
                            probes, for the GPU unit tests only; never linked into the product.
+* ``tests/native/libcpz_partprobe.so`` -- gfx950 build of csrc/part.hip, included unchanged,
+                           behind plain C probes of its kernels (tests/native/partprobe.hip),
+                           for the GPU unit tests only; never linked into the product.
 * ``oracle/``            -- delegated to oracle/Makefile (the C oracle: CPU baseline and
                            at-scale checker; test infrastructure only).
 
@@ -27,6 +30,7 @@ LIBDIR = os.path.join(PKG, "lib")
 LIBCPZ = os.path.join(LIBDIR, "libcpz.so")
 HOSTTEST = os.path.join(ROOT, "tests", "native", "libcpz_hosttest.so")
 DEVPROBE = os.path.join(ROOT, "tests", "native", "libcpz_devprobe.so")
+PARTPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partprobe.so")
 ARCH = os.environ.get("CPZ_OFFLOAD_ARCH", "gfx950")
 
 
@@ -134,6 +138,21 @@ def build_devprobe(force: bool = False, out: str = DEVPROBE, include: str = CSRC
     return out
 
 
+def build_partprobe(force: bool = False, out: str = PARTPROBE, include: str = CSRC) -> str:
+    """Probes of the partitioned check's kernels (tests/native/partprobe.hip, which includes
+    part.hip itself), compiled like the product's units.  `out` / `include` build them over
+    another copy of csrc (a mutated one) for tests/test_gpu_part_probe.py's CPZ_PARTPROBE."""
+    src = os.path.join(ROOT, "tests", "native", "partprobe.hip")
+    deps = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h") or f == "part.hip"]
+    if not force and not _newer(out, [src] + deps):
+        return out
+    tmp = out + ".tmp"
+    _run([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", include,
+          "-I", os.path.join(ROOT, "include"), "-shared", src, "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 CPP_TEST = os.path.join(ROOT, "tests", "cpp", "batch_verifier_test")
 
 
@@ -195,6 +214,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_oracle(force)
     build_libcpz(force, verbose)
     build_devprobe(force)
+    build_partprobe(force)
     build_cpp_test(force)
     build_dropin_test(force)
     build_merge_groups_test(force)

@@ -545,7 +545,7 @@ __global__ void __launch_bounds__(64) k_part_sum2(const ge_p3* tmp, int64_t m, u
 // k_part_index_digits: listed block b, thread t = proof kPartProofs * blocks[b] + t of the
 // prepared batch: the first pass's scalars (weights from the same ChaCha20 block, rlc.hip
 // k_rlc_prepare) times j -- the r-points' j a_i as an integer (nine signed radix-2^16 digits;
-// j < 2^16 - 256 keeps |digit 8| < 2^15 - 128), j a_i c_i mod l and j b_i c_i mod l recoded, and
+// j < 2^16 - 258 keeps |digit 8| < 2^15 - 128), j a_i c_i mod l and j b_i c_i mod l recoded, and
 // the block sums of j a_i s_i, j b_i s_i.  Zero digits and sum terms where the prepare gave zero
 // weight.
 // ---------------------------------------------------------------------------------------
@@ -564,7 +564,7 @@ __device__ __forceinline__ void index_weight_digits(int16_t d[kRlcWindows], cons
 }
 
 __global__ void __launch_bounds__(kPartProofs) k_part_index_digits(PartIdxArgs a) {
-  static_assert(kPartLocJ0 < (1 << 16) - 256 && kPartLocJ0 - 2 * (kPartProofs - 1) > (1 << 15),
+  static_assert(kPartLocJ0 < (1 << 16) - 258 && kPartLocJ0 - 2 * (kPartProofs - 1) > (1 << 15),
                 "index multipliers: digit 8 of j a below 2^15 - 128, and above 2^15 so that it spreads");
   __shared__ sc red_a[kPartProofs];
   __shared__ sc red_b[kPartProofs];

@@ -165,8 +165,10 @@ struct PartArgs {
 // window structure.  The j lie just below 2^16 so that the ninth digit spreads over its range:
 // with j = t + 1 or 2 t + 1 the r-points' ninth digits were small and piled into the lowest
 // buckets of 8-bit windows 16 / 17, and the walk waited for the lane holding them (C5's 15,776
-// failing blocks: 18.1 - 20.9 ms, against 13.4 ms for the same walk with j = 1).
-constexpr int64_t kPartLocJ0 = (1 << 16) - 257;
+// failing blocks: 18.1 - 20.9 ms, against 13.4 ms for the same walk with j = 1).  j <= 2^16 - 259
+// keeps the ninth digit strictly inside 2^15 - 128: the weight whose words are all -32768 gives
+// -(2^15 - 128) exactly at j = 2^16 - 257 (tests/test_part_model.py).
+constexpr int64_t kPartLocJ0 = (1 << 16) - 259;
 #ifndef CPZ_PART_LOCATE
 #define CPZ_PART_LOCATE 1
 #endif
