@@ -109,18 +109,20 @@ def build_clock_probe(force: bool = False) -> str:
     return build_libcpz(force, out=CLOCK_PROBE_LIB, defines=("CPZ_CLOCK_PROBE", "CPZ_TIMING_ONLY"))
 
 
-def build_hosttest(force: bool = False) -> str:
-    srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("hostlib.cpp", "hostlib_joint.cpp")]
-    if not force and not _newer(HOSTTEST, srcs + _headers()):
-        return HOSTTEST
+def build_hosttest(force: bool = False, out: str = HOSTTEST, defines=()) -> str:
+    """`out` / `defines` build a variant of the device library elsewhere (a switch at 0), so that
+    the CPU tests can hold the fallback code to the same checks."""
+    srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("hostlib.cpp", "hostlib_joint.cpp", "hostlib_lean.cpp")]
+    if not force and not _newer(out, srcs + _headers()):
+        return out
     cxx = shutil.which("g++") or "g++"
-    tmp = HOSTTEST + ".tmp"
+    tmp = out + ".tmp"
     # CPZ_HOST_DEFINES: extra -D flags to check a tuning variant of the device library on the CPU
-    extra = ["-D" + d for d in os.environ.get("CPZ_HOST_DEFINES", "").split()]
+    extra = ["-D" + d for d in os.environ.get("CPZ_HOST_DEFINES", "").split() + list(defines)]
     _run([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-DCPZ_BOUNDS_CHECK", "-DCPZ_COUNT_OPS"] + extra +
          ["-I", CSRC] + srcs + ["-o", tmp])
-    os.replace(tmp, HOSTTEST)
-    return HOSTTEST
+    os.replace(tmp, out)
+    return out
 
 
 def build_devprobe(force: bool = False, out: str = DEVPROBE, include: str = CSRC) -> str:

@@ -85,6 +85,21 @@ CPZ_HD ge_cached p3_to_cached(const ge_p3& p) {
   return r;
 }
 
+// 2P from X, Y and 2Z^2: 3S.  dbl-2008-hwcd with a = -1.  (An affine P has 2Z^2 = 2, no square.)
+CPZ_HD ge_p1p1 p2_dbl_zz2(const fe& X, const fe& Y, const fe& ZZ2) {
+  const fe XX = fe_sq(X);
+  const fe YY = fe_sq(Y);
+  const fe XpY2 = fe_sq(fe_add(X, Y));
+  const fe YYpXX = fe_add(YY, XX);
+  const fe YYmXX = fe_sub(YY, XX);
+  ge_p1p1 r;
+  r.X = fe_sub(XpY2, YYpXX);
+  r.Y = YYpXX;
+  r.Z = YYmXX;
+  r.T = fe_sub(ZZ2, YYmXX);
+  return r;
+}
+
 // 2P: 4S (one of them folded as 2Z^2) ; dbl-2008-hwcd with a = -1.
 CPZ_HD ge_p1p1 p2_dbl(const ge_p2& p) {
   const fe XX = fe_sq(p.X);
@@ -155,6 +170,24 @@ CPZ_HD ge_niels ge_niels_cneg(const ge_niels& q, bool neg) {
   r.ypx = fe_select(q.ypx, q.ymx, neg);
   r.ymx = fe_select(q.ymx, q.ypx, neg);
   r.xy2d = fe_select(q.xy2d, fe_neg(q.xy2d), neg);
+  return r;
+}
+
+// a when sign >= 0, -a when sign < 0 (only the sign bit of `sign` is read), as (x ^ m) + c with
+// m = sign >> 31 and c = -m: one v_xad_u32 per limb, where a negation and a select take two.
+CPZ_HD fe fe_cneg(const fe& a, int32_t sign) {
+  const uint32_t m = (uint32_t)(sign >> 31), c = (uint32_t)sign >> 31;
+  fe r;
+#pragma unroll
+  for (int i = 0; i < 10; i++) r.v[i] = (int32_t)(((uint32_t)a.v[i] ^ m) + c);
+  return r;
+}
+
+// -P for sign < 0, P otherwise, on a completed point ((X:Z), (Y:T)): x = X / Z changes sign, and
+// so do X and T of the extended point that p1p1_to_p3 makes of it.
+CPZ_HD ge_p1p1 ge_p1p1_cneg(const ge_p1p1& p, int32_t sign) {
+  ge_p1p1 r = p;
+  r.X = fe_cneg(p.X, sign);
   return r;
 }
 

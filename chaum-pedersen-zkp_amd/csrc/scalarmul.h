@@ -12,6 +12,18 @@
 #include "ristretto.h"
 #include "scalar25519.h"
 
+// Per-proof path (build_joint_table, straus_half_joint, comb_add), each 0 for the form before it:
+//   CPZ_LAZY_SIGN   the sign of a looked-up entry moves to the accumulator: the entry is added
+//                   unmodified and X of the completed running point is negated when the sign changes
+//   CPZ_TABLE_LEAN  check_equation builds the joint table without the slot no window reads and
+//                   without squaring Z = 1
+#ifndef CPZ_LAZY_SIGN
+#define CPZ_LAZY_SIGN 1
+#endif
+#ifndef CPZ_TABLE_LEAN
+#define CPZ_TABLE_LEAN 1
+#endif
+
 namespace cpz {
 
 constexpr int kTableV = 8;     // cached multiples 1..8 of a variable base (radix-16 digits)
@@ -30,8 +42,8 @@ constexpr int64_t kCombPerBase = (int64_t)kCombWindows * kCombStride;
 // Device view of one base's comb (entries in global memory).
 struct CombTable {
   const ge_niels* p;
-  CPZ_HDM ge_niels lookup(int k, int digit) const {
-    const int mag = digit < 0 ? -digit : digit;
+  // entry mag (0..2^15) of window k as stored, no sign applied
+  CPZ_HDM ge_niels lookup_mag(int k, int mag) const {
     const ge_niels* e = p + (int64_t)k * kCombStride + mag;
     ge_niels r;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -42,9 +54,23 @@ struct CombTable {
 #else
     r = *e;
 #endif
-    return ge_niels_cneg(r, digit < 0);
+    return r;
+  }
+  CPZ_HDM ge_niels lookup(int k, int digit) const {
+    return ge_niels_cneg(lookup_mag(k, digit < 0 ? -digit : digit), digit < 0);
   }
 };
+
+// The unsigned entry of any comb: lookup_mag where the comb has one (CombTable), else lookup with
+// the magnitude as its digit (the host stand-ins of the unit tests).
+template <class Comb>
+CPZ_HD auto comb_entry(const Comb& comb, int k, int mag, int) -> decltype(comb.lookup_mag(k, mag)) {
+  return comb.lookup_mag(k, mag);
+}
+template <class Comb>
+CPZ_HD ge_niels comb_entry(const Comb& comb, int k, int mag, long) {
+  return comb.lookup(k, mag);
+}
 
 // Per-proof table of cached points (tab[0] = identity, tab[k] = k P), addressed as a base
 // pointer plus a 32-bit byte offset per entry: entry e at col + 160 e, its 16-byte vectors
@@ -196,8 +222,12 @@ CPZ_HD ge_p3 straus_vartime(const SlabTable& tab_v, const ge_niels* tab_b, const
 
 // Adds [s] B to a pending completed point through the comb (16 mixed additions).
 // sdig: 16 radix-2^16 signed digits (sc_recode_radix65536).
+// Lazy sign: the sum is kept as sigma * cur, sigma = the sign of the last digit added (`sign` on
+// entry: the point handed in is cur when sign >= 0, -cur when sign < 0).  A digit d of sign tau
+// adds the stored entry |d| to (sigma tau) * cur: sigma (cur) + tau E = tau (sigma tau cur + E).
+// The returned point carries its true sign.
 template <class Comb, class Dig>
-CPZ_HD ge_p1p1 comb_add(ge_p1p1 cur, const Comb& comb, const Dig& sd) {
+CPZ_HD ge_p1p1 comb_add(ge_p1p1 cur, const Comb& comb, const Dig& sd, int32_t sign = 0) {
 #pragma unroll 1
   for (int j = 0; j < 8; j++) {
     const uint32_t w = sd[j];
@@ -206,10 +236,16 @@ CPZ_HD ge_p1p1 comb_add(ge_p1p1 cur, const Comb& comb, const Dig& sd) {
 #pragma unroll
     for (int m = 0; m < 2; m++) {
       const int d = (int32_t)(w << (16 - 16 * m)) >> 16;
+#if CPZ_LAZY_SIGN
+      const ge_niels e = comb_entry(comb, 2 * j + m, d < 0 ? -d : d, 0);
+      cur = ge_add_niels(p1p1_to_p3(ge_p1p1_cneg(cur, d ^ sign)), e);
+      sign = d;
+#else
       cur = ge_add_niels(p1p1_to_p3(cur), comb.lookup(2 * j + m, d));
+#endif
     }
   }
-  return cur;
+  return ge_p1p1_cneg(cur, sign);
 }
 
 // Joint table of one equation (see verify.h): the 13 cached combinations a Y' + b R' with
@@ -234,6 +270,18 @@ CPZ_HD int joint_top_window(uint32_t wu3, uint32_t wv3) {
 // One copy of the addition code (the rolled loops over s and j) and one of the doubling code
 // (the loop over d); beside the two affine inputs at most two extended points are live: (1, s)
 // and the one being stored.  (The compiler spills in this function, not in the Straus loop.)
+//
+// kFull = false (what check_equation builds, CPZ_TABLE_LEAN) leaves out what no verdict needs,
+// 5 M + 6 S of the 70 M + 16 S:
+//   slot (2, -2) is neither computed nor stored: no window selects it (a = 2 only stands for
+//     a negated a = -2, whose b is then in -1..2; the top window's digits are not negative);
+//   2 Y and 2 R take 2 Z^2 = 2 instead of squaring Z = 1.  Their doubling is a second copy of the
+//     code, outside the rolled loop: selecting 2 Z^2 inside the one copy cost 100 more spilled
+//     VGPRs (scratch 300 -> 692 B per lane), the peeled form spills less than the full build
+//     (268 B).
+// (Y + R and Y - R also share the product T_Y * 2dT_R, 1 M.  Kept across the loop over s it
+// spilled 4 more VGPRs in the form it was tried in, so it is computed twice.)
+template <bool kFull = true>
 CPZ_HD void build_joint_table(const SlabTable& tab, const ge_p3& Y, const ge_p3& R) {
   ge_niels nY, nR;
   nY.ypx = fe_add(Y.Y, Y.X);
@@ -257,12 +305,21 @@ CPZ_HD void build_joint_table(const SlabTable& tab, const ge_p3& Y, const ge_p3&
       tab.store(j == 0 ? joint_slot(1, s) : (j == 1 ? joint_slot(1, 2 * s) : joint_slot(2, s)), p3_to_cached(Q));
       if (j == 0) A = Q;
     }
+    if constexpr (kFull) {
 #pragma unroll 1
-    for (int d = 0; d < 2; d++) {
-      // d = 0: 2 A = (2, 2 s);  d = 1: 2 Y = (2, 0) in the first pass over s, 2 R = (0, 2) in the second
-      const ge_p3& P = d == 0 ? A : (neg ? R : Y);
-      const int slot = d == 0 ? joint_slot(2, 2 * s) : (neg ? joint_slot(0, 2) : joint_slot(2, 0));
-      tab.store(slot, p3_to_cached(p1p1_to_p3(p2_dbl(ge_p2{P.X, P.Y, P.Z}))));
+      for (int d = 0; d < 2; d++) {
+        // d = 0: 2 A = (2, 2 s);  d = 1: 2 Y = (2, 0) in the first pass over s, 2 R = (0, 2) in the second
+        const ge_p3& P = d == 0 ? A : (neg ? R : Y);
+        const int slot = d == 0 ? joint_slot(2, 2 * s) : (neg ? joint_slot(0, 2) : joint_slot(2, 0));
+        tab.store(slot, p3_to_cached(p1p1_to_p3(p2_dbl(ge_p2{P.X, P.Y, P.Z}))));
+      }
+    } else {
+      // 2 A = (2, 2) in the first pass only: (2, -2) is the slot no window reads
+      if (!neg) tab.store(joint_slot(2, 2), p3_to_cached(p1p1_to_p3(p2_dbl(ge_p2{A.X, A.Y, A.Z}))));
+      // 2 Y = (2, 0) in the first pass, 2 R = (0, 2) in the second: affine points, 2 Z^2 = 2
+      const ge_p3& P = neg ? R : Y;
+      const ge_p1p1 D = p2_dbl_zz2(P.X, P.Y, fe_add(fe_one(), fe_one()));
+      tab.store(neg ? joint_slot(0, 2) : joint_slot(2, 0), p3_to_cached(p1p1_to_p3(D)));
     }
   }
 }
@@ -289,6 +346,12 @@ template <class Comb, class Dig>
 CPZ_HD ge_p1p1 straus_half_joint(const SlabTable& tab, const Comb& comb, const Dig& ud, const Dig& vd,
                                  const Dig& sdig) {
   ge_p1p1 cur = cached_to_p1p1(tab.load(joint_top_window(ud[3], vd[3])));
+  // Lazy sign: the sum so far is sigma * cur, sigma = the sign of the last window's slot (the
+  // top window's is +, and so is slot 0's).  A window of sign tau adds the stored entry to
+  // (sigma tau) * 4 cur -- doublings commute with the sign -- and leaves sigma = tau:
+  //   sigma (4 cur) + tau E = tau (sigma tau (4 cur) + E).
+  // Negating X of the completed point negates X and T of its extended form, the point's negative.
+  int32_t sign = 0;
 #pragma unroll 1
   for (int j = 3; j >= 0; j--) {
     const uint32_t wu = ud[j], wv = vd[j];
@@ -296,9 +359,18 @@ CPZ_HD ge_p1p1 straus_half_joint(const SlabTable& tab, const Comb& comb, const D
     for (int m = j == 3 ? 14 : 15; m >= 0; m--) {
       // the table load issued before the two doublings, which hide part of its latency
       // (the table lives in the HBM-backed scratch slab)
-      const ge_cached e = cached_lookup(tab, joint_window(wu, wv, m));
+      const int slot = joint_window(wu, wv, m);
+#if CPZ_LAZY_SIGN
+      const ge_cached e = tab.load(slot < 0 ? -slot : slot);
+#else
+      const ge_cached e = cached_lookup(tab, slot);
+#endif
       cur = p2_dbl(p1p1_to_p2(cur));
       cur = p2_dbl(p1p1_to_p2(cur));
+#if CPZ_LAZY_SIGN
+      cur.X = fe_cneg(cur.X, slot ^ sign);
+      sign = slot;
+#endif
 #if defined(CPZ_EXP_NIELS_TABLES)
       // timing experiment only (timing_only.h: wrong verdicts): the entry added as an affine
       // Niels point, Z never read -- the best case of normalised per-proof tables
@@ -308,7 +380,7 @@ CPZ_HD ge_p1p1 straus_half_joint(const SlabTable& tab, const Comb& comb, const D
 #endif
     }
   }
-  return comb_add(cur, comb, sdig);
+  return comb_add(cur, comb, sdig, sign);
 }
 
 // [s] B through the comb (prover path): 16 mixed additions.

@@ -295,7 +295,7 @@ CPZ_EQ_LOOP
     P = (k && vneg) ? P : ge_neg(P);
     if (k) Rp = P; else Yp = P;
   }
-  build_joint_table(tab, Yp, Rp);
+  build_joint_table<CPZ_TABLE_LEAN == 0>(tab, Yp, Rp);  // lean: the never-read slot left unwritten
   if constexpr (kPre) {
     r_identity = false;
   } else {
