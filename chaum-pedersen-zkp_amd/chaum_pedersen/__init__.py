@@ -472,6 +472,31 @@ class Gpu:
             _ptr(present), bytes(seed), first_index, partial, ctypes.byref(ok), _ptr(out)))
         return partial.raw, bool(ok.value), out
 
+    def verify_batch_pairs(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, seed: bytes,
+                           first_index: int = 0, contexts=None, statuses: bool = True,
+                           equations_only: bool = False):
+        """RLC batch check where entry i stands under pairs[pair_idx[i]], all in one MSM
+        (cpz_verify_batch_pairs_ex): at most PAIRS_MAX pairs and BATCH_PAIRS_MAX_PROOFS proofs.
+        Returns (partial: bytes, batch_ok: bool, status: uint8[n] or None) as verify_batch does;
+        the partial is the sum over the pairs of verify_batch's partial over that pair's entries,
+        weights keyed by first_index + the entry's position here.  A batch that passes builds no
+        table for any pair.  With statuses=True a failing batch runs the fallback search and each
+        status is what verify_each_pairs returns for that entry.  pair_idx: n integers in
+        [0, len(pairs)), checked here before the library is called."""
+        n = len(y1)
+        npairs = len(pairs)
+        idx = _pair_indices(pair_idx, n, npairs)
+        arrs = [_rows(a, n, nm) for a, nm in ((y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2"), (s, "s"))]
+        gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+        blob, off, present = _ctx_arrays(contexts, n)
+        partial = ctypes.create_string_buffer(32)
+        ok = ctypes.c_int(0)
+        out = np.empty(n, dtype=np.uint8) if statuses else None
+        _native.check(self._lib.cpz_verify_batch_pairs_ex(
+            self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
+            _ptr(off), _ptr(present), bytes(seed), first_index, partial, ctypes.byref(ok), _ptr(out)))
+        return partial.raw, bool(ok.value), out
+
     def verify_batch_device(self, y1, y2, r1, r2, s, status_out, seed: bytes, first_index: int = 0,
                             fallback: bool = False, params: Optional[Parameters] = None,
                             stream: Optional[int] = None, ctx_bytes=None, ctx_off=None, ctx_present=None):

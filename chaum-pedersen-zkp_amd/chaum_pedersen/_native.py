@@ -35,10 +35,11 @@ EXPORTED = (
     "cpz_verify_response", "cpz_verify_response_device", "cpz_prove", "cpz_prove_device", "cpz_decode_points",
     "cpz_abi_version", "cpz_ctx_set_commitment_checks", "cpz_ctx_stage_times_n", "cpz_ctx_fallback_stats",
     "cpz_verify_each_ex", "cpz_verify_batch_ex", "cpz_verify_response_ex",
-    "cpz_verify_each_pairs", "cpz_verify_each_pairs_ex",
+    "cpz_verify_each_pairs", "cpz_verify_each_pairs_ex", "cpz_verify_batch_pairs", "cpz_verify_batch_pairs_ex",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
+BATCH_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_BATCH_PAIRS_MAX_PROOFS: proofs per cpz_verify_batch_pairs call
 CALL_EQUATIONS_ONLY = 1   # CPZ_CALL_EQUATIONS_ONLY: commitment checks off for one call
 NUM_STAGES = 16
 FALLBACK_STATS = 8
@@ -96,6 +97,12 @@ def _declare(lib):
     lib.cpz_verify_batch_ex.restype = ctypes.c_int
     lib.cpz_verify_batch_ex.argtypes = ([_p, ctypes.c_uint32, _p, _p, ctypes.c_size_t] + [_p] * 5 +
                                         [_p, _p, _p, _p, ctypes.c_uint64, _p, ctypes.POINTER(ctypes.c_int), _p])
+    lib.cpz_verify_batch_pairs.restype = ctypes.c_int
+    lib.cpz_verify_batch_pairs.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p] + [_p] * 5 +
+                                           [_p, _p, _p, _p, ctypes.c_uint64, _p, ctypes.POINTER(ctypes.c_int), _p])
+    lib.cpz_verify_batch_pairs_ex.restype = ctypes.c_int
+    lib.cpz_verify_batch_pairs_ex.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] + [_p] * 5 +
+                                              [_p, _p, _p, _p, ctypes.c_uint64, _p, ctypes.POINTER(ctypes.c_int), _p])
     lib.cpz_verify_each_multi.restype = ctypes.c_int
     lib.cpz_verify_each_multi.argtypes = [_p, ctypes.c_int, _p, _p, ctypes.c_size_t] + [_p] * 5 + [_p, _p, _p, _p]
     lib.cpz_verify_batch_multi.restype = ctypes.c_int

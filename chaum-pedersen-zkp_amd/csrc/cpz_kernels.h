@@ -195,6 +195,16 @@ struct PairArgs {
   const uint32_t* pair_idx = nullptr;  // n indices into desc
 };
 
+// Mixed-pair batch check (cpz_verify_batch_pairs): what k_pair_setup leaves per pair for the host
+// -- the two transcript snapshots and whether g and h decoded -- read back in one copy for all
+// pairs.  The pairs' affine Niels points (the MSM's extra points) stay on the device.
+struct PairSetup {
+  StrobeSnap prefix[2];          // [0] after Transcript::new(), [1] after append_parameters
+  int32_t ok[2];                 // g, h decoded
+  int32_t pad[2];
+};
+static_assert(sizeof(PairSetup) % 16 == 0, "setup rows stay 16-byte aligned");
+
 struct ProveArgs {
   int64_t n;
   uint64_t first_index;
@@ -213,6 +223,12 @@ struct ProveArgs {
 
 hipError_t launch_transcript_prefix(const uint32_t* gh_words, StrobeSnap* out, hipStream_t st);
 hipError_t launch_challenge(const ChallengeArgs& a, hipStream_t st);
+// Every pair of a mixed-pair batch check in one launch (a workgroup per pair): the transcript
+// snapshots and decode flags into out[p], g_p and h_p as affine Niels points into pts[2 p ..].
+hipError_t launch_pair_setup(const uint32_t* gh_words, int npairs, PairSetup* out, ge_niels* pts, hipStream_t st);
+// k_challenge with a pair per proof (PairArgs; the descriptors' tables may be null): a's prefix,
+// gh_words and masks are unused.
+hipError_t launch_challenge_pairs(const ChallengeArgs& a, const PairArgs& pa, hipStream_t st);
 hipError_t launch_probe_gather(const ProbeGatherArgs& a, hipStream_t st);
 bool challenge_prefix_is_fixed(const StrobeSnap& snap);  // the no-context fast path applies
 bool challenge_prefix_is_ctx32(const StrobeSnap& snap);  // prefix[0]: the 32-byte-context fast path applies

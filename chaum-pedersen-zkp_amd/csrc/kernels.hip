@@ -68,15 +68,46 @@ __global__ void k_transcript_prefix(const uint32_t* __restrict__ gh_words, Strob
   out[1].pos = s.pos; out[1].pos_begin = s.pos_begin; out[1].flags = s.cur_flags;
 }
 
+// Mixed-pair batch check: workgroup p serves pair p of the call, a wave per chain -- wave 0 the
+// transcript snapshots (k_transcript_prefix's, on an LDS image of the sponge), waves 1 and 2
+// the decodes of g_p and h_p into affine Niels points (the MSM's extra points) and their flags.
+__global__ void __launch_bounds__(64 * 3) k_pair_setup(const uint32_t* __restrict__ gh_words,
+                                                       PairSetup* __restrict__ out, ge_niels* __restrict__ pts) {
+  __shared__ uint32_t sponge[50];
+  if ((threadIdx.x & 63) != 0) return;
+  const int p = blockIdx.x, w = threadIdx.x >> 6;
+  const uint32_t* gh = gh_words + 16 * p;
+  if (w == 0) {
+    LdsState st{sponge, 0, 1};
+    Strobe<LdsState> s = transcript_new(st);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(out[p].prefix[0].state);
+    for (int k = 0; k < 50; k++) dst[k] = sponge[k];
+    out[p].prefix[0].pos = s.pos; out[p].prefix[0].pos_begin = s.pos_begin; out[p].prefix[0].flags = s.cur_flags;
+    transcript_parameters(s, gh, gh + 8);
+    dst = reinterpret_cast<uint32_t*>(out[p].prefix[1].state);
+    for (int k = 0; k < 50; k++) dst[k] = sponge[k];
+    out[p].prefix[1].pos = s.pos; out[p].prefix[1].pos_begin = s.pos_begin; out[p].prefix[1].flags = s.cur_flags;
+  } else {
+    const int e = w - 1;
+    uint32_t enc[8];
+    load_words8(enc, gh, e);
+    ge_p3 P;
+    out[p].ok[e] = ristretto_decode(P, enc) ? 1 : 0;
+    store_niels(pts + 2 * p + e, niels_from_p3_affine(P, false));
+  }
+}
+
 constexpr int kChallengeBlock = 128;
 
 // Generic transcript tail: the byte-wise STROBE code on this thread's dword-interleaved
-// image of the sponge in LDS (any context length).
-__device__ __forceinline__ sc challenge_generic(const ChallengeArgs& a, uint32_t* lds, bool has_ctx, uint64_t b0,
+// image of the sponge in LDS (any context length).  prefix / gh_words: the call's, or in pair
+// mode the proof's own pair's.
+__device__ __forceinline__ sc challenge_generic(const ChallengeArgs& a, const StrobeSnap* prefix,
+                                                const uint32_t* gh_words, uint32_t* lds, bool has_ctx, uint64_t b0,
                                                 uint64_t b1, const uint32_t y1[8], const uint32_t y2[8],
                                                 const uint32_t r1[8], const uint32_t r2[8]) {
   LdsState st{lds, (int)threadIdx.x, kChallengeBlock};
-  const StrobeSnap& snap = a.prefix[has_ctx ? 0 : 1];
+  const StrobeSnap& snap = prefix[has_ctx ? 0 : 1];
   {
     const uint32_t* src = reinterpret_cast<const uint32_t*>(snap.state);
 #pragma unroll
@@ -85,15 +116,21 @@ __device__ __forceinline__ sc challenge_generic(const ChallengeArgs& a, uint32_t
   Strobe<LdsState> s(st, snap.pos, snap.pos_begin, (uint8_t)snap.flags);
   if (has_ctx) {
     transcript_context(s, a.ctx_bytes + b0, (uint32_t)(b1 - b0));
-    transcript_parameters(s, a.gh_words, a.gh_words + 8);
+    transcript_parameters(s, gh_words, gh_words + 8);
   }
   return transcript_challenge(s, y1, y2, r1, r2);
 }
 
-__global__ void __launch_bounds__(kChallengeBlock) k_challenge(ChallengeArgs a) {
-  __shared__ uint32_t lds[50 * kChallengeBlock];
+// kPairs (k_challenge_pairs): proof i takes the transcript prefixes, generator words, fast_noctx /
+// fast_ctx32 and masks from pa.desc[pa.pair_idx[i]] instead of a's (kPairs is a constant: one arm
+// of each read is compiled, so k_challenge stays what it was).
+template <bool kPairs>
+__device__ __forceinline__ void challenge_body(const ChallengeArgs& a, const PairArgs& pa, uint32_t* lds) {
+#define CPZ_PAIR_FIELD(f) (kPairs ? pd->f : a.f)
   const int64_t i = (int64_t)blockIdx.x * kChallengeBlock + threadIdx.x;
   if (i >= a.n) return;
+  const PairDesc* pd = nullptr;
+  if constexpr (kPairs) pd = pa.desc + pa.pair_idx[i];
   const bool has_ctx = a.ctx_off != nullptr && (a.ctx_present == nullptr || a.ctx_present[i] != 0);
   uint32_t y1[8], y2[8], r1[8], r2[8];
   load_words8(y1, a.y1, i);
@@ -104,21 +141,23 @@ __global__ void __launch_bounds__(kChallengeBlock) k_challenge(ChallengeArgs a) 
   const uint64_t b1 = has_ctx ? (a.ctx_end ? a.ctx_end[i] : a.ctx_off[i + 1]) : 0;
   // Entries on a fixed schedule skip the LDS sponge: no context (k_challenge_noctx's tail)
   // or a 4-byte-aligned 32-byte context (the service's challenge ids).
-  const bool fixed_noctx = !has_ctx && a.fast_noctx;
+  const bool fixed_noctx = !has_ctx && CPZ_PAIR_FIELD(fast_noctx);
   // (the context's own address must be 4-byte aligned: the base pointer is the caller's)
-  const bool fixed_ctx32 = has_ctx && a.fast_ctx32 && b1 - b0 == 32 &&
+  const bool fixed_ctx32 = has_ctx && CPZ_PAIR_FIELD(fast_ctx32) && b1 - b0 == 32 &&
                            ((reinterpret_cast<uintptr_t>(a.ctx_bytes) + b0) & 3) == 0;
   sc c;
   if (fixed_noctx) {
-    c = challenge_fixed(reinterpret_cast<const uint32_t*>(a.prefix[1].state), a.k1, a.k2, y1, y2, r1, r2);
+    c = challenge_fixed(reinterpret_cast<const uint32_t*>(CPZ_PAIR_FIELD(prefix)[1].state), CPZ_PAIR_FIELD(k1),
+                        CPZ_PAIR_FIELD(k2), y1, y2, r1, r2);
   } else if (fixed_ctx32) {
     uint32_t cw[8];
     const uint32_t* cp = reinterpret_cast<const uint32_t*>(a.ctx_bytes + b0);  // 4-byte aligned (above)
 #pragma unroll
     for (int k = 0; k < 8; k++) cw[k] = cp[k];
-    c = challenge_fixed_ctx32(reinterpret_cast<const uint32_t*>(a.prefix[0].state), a.c32, cw, y1, y2, r1, r2);
+    c = challenge_fixed_ctx32(reinterpret_cast<const uint32_t*>(CPZ_PAIR_FIELD(prefix)[0].state), CPZ_PAIR_FIELD(c32),
+                              cw, y1, y2, r1, r2);
   } else {
-    c = challenge_generic(a, lds, has_ctx, b0, b1, y1, y2, r1, r2);
+    c = challenge_generic(a, CPZ_PAIR_FIELD(prefix), CPZ_PAIR_FIELD(gh_words), lds, has_ctx, b0, b1, y1, y2, r1, r2);
   }
   store_words8(a.c_out, i, c.w);
   if (a.s != nullptr) {
@@ -126,6 +165,17 @@ __global__ void __launch_bounds__(kChallengeBlock) k_challenge(ChallengeArgs a) 
     load_words8(w, a.s, i);
     a.status_out[i] = response_status(w, a.eq_only != 0);
   }
+#undef CPZ_PAIR_FIELD
+}
+
+__global__ void __launch_bounds__(kChallengeBlock) k_challenge(ChallengeArgs a) {
+  __shared__ uint32_t lds[50 * kChallengeBlock];
+  challenge_body<false>(a, PairArgs{}, lds);
+}
+
+__global__ void __launch_bounds__(kChallengeBlock) k_challenge_pairs(ChallengeArgs a, PairArgs pa) {
+  __shared__ uint32_t lds[50 * kChallengeBlock];
+  challenge_body<true>(a, pa, lds);
 }
 // No-context fast path (verify.h, challenge_fixed): the sponge in 50 registers, the
 // framing as two constant masks, two permutations, no LDS.  Chosen by the runtime when the
@@ -505,6 +555,20 @@ __global__ void __launch_bounds__(256) k_response_prep(int64_t n, const uint32_t
 // ---------------------------------------------------------------------------------------
 hipError_t launch_transcript_prefix(const uint32_t* gh_words, StrobeSnap* out, hipStream_t st) {
   hipLaunchKernelGGL(k_transcript_prefix, dim3(1), dim3(64), 0, st, gh_words, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_pair_setup(const uint32_t* gh_words, int npairs, PairSetup* out, ge_niels* pts, hipStream_t st) {
+  if (npairs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pair_setup, dim3((unsigned)npairs), dim3(64 * 3), 0, st, gh_words, out, pts);
+  return hipGetLastError();
+}
+
+hipError_t launch_challenge_pairs(const ChallengeArgs& a, const PairArgs& pa, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (!pa.desc || !pa.pair_idx || a.ctx_end) return hipErrorInvalidValue;
+  const int64_t blocks = (a.n + kChallengeBlock - 1) / kChallengeBlock;
+  hipLaunchKernelGGL(k_challenge_pairs, dim3((unsigned)blocks), dim3(kChallengeBlock), 0, st, a, pa);
   return hipGetLastError();
 }
 

@@ -34,7 +34,7 @@ constexpr int64_t kRlcMinHeads = 2048;   // head slots per window whatever the M
 #define CPZ_RLC_SPARSE 1
 #endif
 constexpr int kRlcSparsePts = 2048;      // MSMs of at most this many points reduce their non-empty buckets only
-// Points of one MSM (its flat positions t, incl. the two extras): the 32-bit entries hold t
+// Points of one MSM (its flat positions t, incl. the extras): the 32-bit entries hold t
 // in 24 bits and all-ones is their empty marker.
 constexpr int64_t kRlcMaxMsmPoints = (1ll << 24) - 1;
 
@@ -57,11 +57,15 @@ struct RlcPrepArgs {
   int* any_bad;                  // set to 1 if some proof has a non-zero decode-level status
   int eq_only = 0;               // commitment checks off: identity r1 / r2 keep their weight
   uint64_t* clock_probe = nullptr;  // CPZ_CLOCK_PROBE builds only: 5 words per wave (rlc_dev.h)
+  sc* prod = nullptr;            // pair mode (launch_rlc_prepare_pairs): [n][2] a_i s_i, b_i s_i per proof,
+                                 // zero where the proof carries no weight; block_sums / quarter_sums unused
 };
 
 struct RlcMsmArgs {
   int64_t p0, p1;                // point range [p0, p1)
-  int64_t e0;                    // the two extra points (g, h) live at e0, e0 + 1
+  int64_t e0;                    // the extra points live at e0 .. e0 + nextra: (g, h), or in pair
+                                 // mode (g_p, h_p) of pair p at e0 + 2 p, e0 + 2 p + 1
+  int nextra = 2;                // their number: 2, or twice the pairs of a mixed-pair batch check
   ge_niels* pts;
   int16_t* digits;
   int64_t dstride;
@@ -213,6 +217,19 @@ hipError_t launch_part_sum(const ge_p3* part, int64_t nblk, ge_p3* tmp, uint32_t
                            hipStream_t st);
 
 hipError_t launch_rlc_prepare(const RlcPrepArgs& a, hipStream_t st);
+// The same prepare for a mixed-pair batch (challenges from k_challenge_pairs): the per-block sums
+// of a s and b s cannot be pooled across pairs, so every proof's two products go to a.prod.
+hipError_t launch_rlc_prepare_pairs(const RlcPrepArgs& a, hipStream_t st);
+// The extra points of a mixed-pair MSM over proofs [lo, hi): pair p's points gh[2 p], gh[2 p + 1]
+// (k_pair_setup) with the sums of prod[2 i], prod[2 i + 1] over the i in [lo, hi) with
+// pair_idx[i] == p as scalars.  RlcMsmArgs::nextra must be 2 npairs.
+struct RlcPairExtra {
+  const sc* prod;
+  const uint32_t* pair_idx;
+  int64_t lo, hi;
+  const ge_niels* gh;
+  int npairs;
+};
 // Sort and accumulation geometry for `npts` MSM points: sets a.groups / a.chunk / a.echunk.
 void rlc_sort_geometry(RlcMsmArgs& a, int64_t npts);
 // marks (optional, timing): kRlcMsmMarks events recorded on `st` at the phase boundaries
@@ -222,9 +239,10 @@ constexpr int kRlcMsmMarks = 6;
 // final_wait / final_done (overlapped spans, runtime.hip rlc_range_launch): the stream waits for
 // final_wait before k_rlc_final (the previous span's final, which owns RlcMsmArgs::total) and
 // records final_done after it; everything before the final overlaps freely.
+// px (a mixed-pair batch): the extras are px's, block_sums / b0 / b1 / tab are unused.
 hipError_t launch_rlc_msm(const RlcMsmArgs& a, const sc* block_sums, int64_t b0, int64_t b1, const ge_niels* tab,
                           hipStream_t st, hipEvent_t* marks = nullptr, hipEvent_t final_wait = nullptr,
-                          hipEvent_t final_done = nullptr);
+                          hipEvent_t final_done = nullptr, const RlcPairExtra* px = nullptr);
 hipError_t launch_msm_load(int64_t n, const uint32_t* pts_enc, const uint32_t* scalars, ge_niels* pts,
                            int16_t* digits, int64_t dstride, int* bad, hipStream_t st);
 hipError_t launch_rlc_combine(const uint32_t* parts, int k, uint32_t* out, int* flags, hipStream_t st);

@@ -17,7 +17,9 @@
 //   k_rlc_prepare   1 thread / proof: 4 decodes, weights, 4 scalar products, negated
 //                   affine-Niels points, signed radix-2^16 digits (16 windows), per-block
 //                   sums of a_i s_i and b_i s_i.
-//   k_rlc_extra     g and h as two more MSM points with the summed scalars.
+//   k_rlc_extra     g and h as two more MSM points with the summed scalars (a mixed-pair batch,
+//                   cpz_verify_batch_pairs: k_rlc_prepare*_pairs keep each proof's products and
+//                   k_rlc_extra_pairs sums them per pair into 2 npairs such points).
 //   k_rlc_hist      per-(chunk, window) bucket histograms (LDS, 32768 buckets).
 //   k_rlc_bscan     per-bucket prefix over chunks; bucket totals.
 //   k_rlc_scan      exclusive scan -> bucket offsets.
@@ -49,8 +51,14 @@ namespace cpz {
 // Points are decoded one at a time and written out immediately (register pressure: one
 // decoded point live, not four).  A proof that turns out not to be live afterwards gets
 // all its digits zeroed, so its (possibly garbage) Niels entries never enter a bucket.
-__global__ void __launch_bounds__(kRlcPrepBlock, 2) k_rlc_prepare(RlcPrepArgs a) {
-  __shared__ sc red_a[kRlcPrepBlock];
+// kPairs (k_rlc_prepare_pairs, a mixed-pair batch): the challenges are each proof's own pair's,
+// and the sums of a s and b s cannot be pooled over a block whose proofs carry different pairs --
+// every proof's two products go to a.prod instead (zero for a proof without weight) and
+// k_rlc_extra_pairs adds them per pair; no LDS, no block sums.  kPairs is a constant, so
+// k_rlc_prepare keeps its code.
+template <bool kPairs>
+__device__ __forceinline__ void rlc_prepare_body(const RlcPrepArgs& a) {
+  __shared__ sc red_a[kRlcPrepBlock];  // (unused, and so not allocated, in pair mode)
   __shared__ sc red_b[kRlcPrepBlock];
   const int64_t i = (int64_t)blockIdx.x * kRlcPrepBlock + threadIdx.x;
   ClockStamp clk;
@@ -58,8 +66,10 @@ __global__ void __launch_bounds__(kRlcPrepBlock, 2) k_rlc_prepare(RlcPrepArgs a)
   sc zero;
 #pragma unroll
   for (int k = 0; k < 8; k++) zero.w[k] = 0;
-  red_a[threadIdx.x] = zero;
-  red_b[threadIdx.x] = zero;
+  if constexpr (!kPairs) {
+    red_a[threadIdx.x] = zero;
+    red_b[threadIdx.x] = zero;
+  }
   if (i < a.n) {
     // All scalar work first -- weights (replacing random_scalar, batch.rs:240: one ChaCha20
     // block per proof), the four points' digits and the block-sum terms a s, b s (parked in
@@ -88,8 +98,13 @@ __global__ void __launch_bounds__(kRlcPrepBlock, 2) k_rlc_prepare(RlcPrepArgs a)
 #pragma unroll
         for (int wv = 0; wv < kRlcWindows; wv++) a.digits[(int64_t)wv * a.dstride + 4 * i + q] = d[wv];
       }
-      red_a[threadIdx.x] = sc_mul(wa, sv);
-      red_b[threadIdx.x] = sc_mul(wb, sv);
+      if constexpr (kPairs) {
+        a.prod[2 * i] = sc_mul(wa, sv);
+        a.prod[2 * i + 1] = sc_mul(wb, sv);
+      } else {
+        red_a[threadIdx.x] = sc_mul(wa, sv);
+        red_b[threadIdx.x] = sc_mul(wb, sv);
+      }
     }
     bool ok = true, ident = false;
 #pragma unroll 1
@@ -112,14 +127,20 @@ __global__ void __launch_bounds__(kRlcPrepBlock, 2) k_rlc_prepare(RlcPrepArgs a)
     a.status[i] = st;
     if (st != kStOk) {  // zero weight: no digits, no block-sum terms
       atomicOr(a.any_bad, 1);
-      red_a[threadIdx.x] = zero;
-      red_b[threadIdx.x] = zero;
+      if constexpr (kPairs) {
+        a.prod[2 * i] = zero;
+        a.prod[2 * i + 1] = zero;
+      } else {
+        red_a[threadIdx.x] = zero;
+        red_b[threadIdx.x] = zero;
+      }
       for (int q = 0; q < 4; q++)
 #pragma unroll
         for (int wv = 0; wv < kRlcWindows; wv++) a.digits[(int64_t)wv * a.dstride + 4 * i + q] = 0;
     }
   }
   clk.stop(a.clock_probe, i >> 6);
+  if constexpr (kPairs) return;
   // block sums of a_i s_i, b_i s_i (mod l), one per kRlcSumBlock proofs (two per workgroup)
   static_assert(kRlcPrepBlock == 2 * kRlcSumBlock, "two block sums per prepare workgroup");
   __syncthreads();
@@ -137,22 +158,36 @@ __global__ void __launch_bounds__(kRlcPrepBlock, 2) k_rlc_prepare(RlcPrepArgs a)
   }
 }
 
+__global__ void __launch_bounds__(kRlcPrepBlock, 2) k_rlc_prepare(RlcPrepArgs a) { rlc_prepare_body<false>(a); }
+
+// One wave per SIMD asked for, not k_rlc_prepare's two: at two (256 VGPRs) the decode loop spills
+// 12 VGPRs to scratch, as k_rlc_prepare's spills 10; here the same values sit in 29 AGPRs and the
+// kernel has no scratch (profiles/batch_pairs_resource_usage.txt).
+__global__ void __launch_bounds__(kRlcPrepBlock, 1) k_rlc_prepare_pairs(RlcPrepArgs a) {
+  rlc_prepare_body<true>(a);
+}
+
 // Small batches (launch_rlc_prepare: n <= kRlcPrepWideMax): four lanes per proof -- lane q
 // writes point q's digits and decodes point q -- so a BatchVerifier-sized batch waits for one
 // decode per lane instead of four in sequence (on one lane per proof the prepare took 0.28 -
 // 0.37 ms at n = 1 .. 1000, a latency, with most of the chip idle).  The weights' ChaCha20
 // block is recomputed by each of the four lanes.  A block is 64 proofs: its a s and b s sums
 // go to quarter_sums, and k_rlc_bsum4 adds each 128-proof block's two into block_sums.
-__global__ void __launch_bounds__(256, 2) k_rlc_prepare4(RlcPrepArgs a) {
-  __shared__ sc red_a[64];
+// kPairs (k_rlc_prepare4_pairs): as rlc_prepare_body's -- lanes 0 and 2 of a live proof write its
+// products a s and b s to a.prod, no quarter sums.
+template <bool kPairs>
+__device__ __forceinline__ void rlc_prepare4_body(const RlcPrepArgs& a) {
+  __shared__ sc red_a[64];  // (unused, and so not allocated, in pair mode)
   __shared__ sc red_b[64];
   const int q = threadIdx.x & 3, p = threadIdx.x >> 2;
   const int64_t i = (int64_t)blockIdx.x * 64 + p;
   sc zero;
 #pragma unroll
   for (int k = 0; k < 8; k++) zero.w[k] = 0;
-  if (q == 0) red_a[p] = zero;
-  if (q == 2) red_b[p] = zero;
+  if constexpr (!kPairs) {
+    if (q == 0) red_a[p] = zero;
+    if (q == 2) red_b[p] = zero;
+  }
   bool ok = true, ident = false;
   if (i < a.n) {
     {
@@ -170,7 +205,10 @@ __global__ void __launch_bounds__(256, 2) k_rlc_prepare4(RlcPrepArgs a) {
         for (int wv = 0; wv < kRlcWindows; wv++) d[wv] = wv < 8 ? (int16_t)(u[wv >> 1] >> (16 * (wv & 1))) : (int16_t)0;
         sc sv;
         rlc_load8(sv.w, a.s, i);
-        (q == 0 ? red_a : red_b)[p] = sc_mul(rlc_weight(u), sv);
+        if constexpr (kPairs)
+          a.prod[2 * i + (q >> 1)] = sc_mul(rlc_weight(u), sv);
+        else
+          (q == 0 ? red_a : red_b)[p] = sc_mul(rlc_weight(u), sv);
       }
 #pragma unroll
       for (int wv = 0; wv < kRlcWindows; wv++) a.digits[(int64_t)wv * a.dstride + 4 * i + q] = d[wv];
@@ -197,15 +235,18 @@ __global__ void __launch_bounds__(256, 2) k_rlc_prepare4(RlcPrepArgs a) {
     else st = kStOk;
     if (q == 0) a.status[i] = st;  // after the quad's loads of it: one wave, in program order
     if (st != kStOk) {  // zero weight: no digits, no block-sum terms
-      if (q == 0) {
-        atomicOr(a.any_bad, 1);
-        red_a[p] = zero;
+      if (q == 0) atomicOr(a.any_bad, 1);
+      if constexpr (kPairs) {
+        if (!(q & 1)) a.prod[2 * i + (q >> 1)] = zero;
+      } else {
+        if (q == 0) red_a[p] = zero;
+        if (q == 2) red_b[p] = zero;
       }
-      if (q == 2) red_b[p] = zero;
 #pragma unroll
       for (int wv = 0; wv < kRlcWindows; wv++) a.digits[(int64_t)wv * a.dstride + 4 * i + q] = 0;
     }
   }
+  if constexpr (kPairs) return;
   __syncthreads();
   for (int off = 32; off > 0; off >>= 1) {
     if (threadIdx.x < off) {
@@ -218,6 +259,12 @@ __global__ void __launch_bounds__(256, 2) k_rlc_prepare4(RlcPrepArgs a) {
     a.quarter_sums[2 * blockIdx.x] = red_a[0];
     a.quarter_sums[2 * blockIdx.x + 1] = red_b[0];
   }
+}
+
+__global__ void __launch_bounds__(256, 2) k_rlc_prepare4(RlcPrepArgs a) { rlc_prepare4_body<false>(a); }
+
+__global__ void __launch_bounds__(256, 2) k_rlc_prepare4_pairs(RlcPrepArgs a) {
+  rlc_prepare4_body<true>(a);
 }
 
 // block_sums of a wide prepare: sum block b (kRlcSumBlock = 128 proofs) is quarters 2 b and
@@ -271,7 +318,49 @@ __global__ void __launch_bounds__(256) k_rlc_extra(RlcMsmArgs a, const sc* __res
   }
 }
 
-// point index for flat position t over [p0, p1) U [e0, e0 + 2)
+// Mixed-pair batches: workgroup p strides over pair_idx[lo .. hi), adds the products of the proofs
+// under pair p (zero for a proof without weight) and writes the pair's two MSM points e0 + 2 p
+// (g_p) and e0 + 2 p + 1 (h_p) with the sums' digits.  A pair without entries in the range gets
+// zero digits: its points enter no bucket.  No atomics: each pair's sum is one workgroup's tree.
+__global__ void __launch_bounds__(256) k_rlc_extra_pairs(RlcMsmArgs a, RlcPairExtra x) {
+  __shared__ sc red_a[256];
+  __shared__ sc red_b[256];
+  const uint32_t p = blockIdx.x;
+  sc sa, sb;
+#pragma unroll
+  for (int k = 0; k < 8; k++) { sa.w[k] = 0; sb.w[k] = 0; }
+  for (int64_t i = x.lo + threadIdx.x; i < x.hi; i += 256) {
+    if (x.pair_idx[i] != p) continue;
+    sa = sc_add(sa, x.prod[2 * i]);
+    sb = sc_add(sb, x.prod[2 * i + 1]);
+  }
+  red_a[threadIdx.x] = sa;
+  red_b[threadIdx.x] = sb;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) {
+      red_a[threadIdx.x] = sc_add(red_a[threadIdx.x], red_a[threadIdx.x + off]);
+      red_b[threadIdx.x] = sc_add(red_b[threadIdx.x], red_b[threadIdx.x + off]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 2) {
+    const sc s = threadIdx.x == 0 ? red_a[0] : red_b[0];
+    const int64_t j = a.e0 + 2 * (int64_t)p + threadIdx.x;
+    {  // the point as it stands, 16 bytes at a time (a ge_niels value indexed by the lane went through scratch)
+      const uint4* src = reinterpret_cast<const uint4*>(x.gh + 2 * p + threadIdx.x);
+      uint4* dst = reinterpret_cast<uint4*>(a.pts + j);
+#pragma unroll
+      for (int k = 0; k < (int)(sizeof(ge_niels) / 16); k++) dst[k] = src[k];
+    }
+    int16_t d[kRlcWindows];
+    recode16(d, s.w);
+#pragma unroll
+    for (int wv = 0; wv < kRlcWindows; wv++) a.digits[(int64_t)wv * a.dstride + j] = d[wv];
+  }
+}
+
+// point index for flat position t over [p0, p1) U [e0, e0 + nextra)
 __device__ __forceinline__ int64_t msm_point(const RlcMsmArgs& a, int64_t t) {
   const int64_t np = a.p1 - a.p0;
   return t < np ? a.p0 + t : a.e0 + (t - np);
@@ -292,7 +381,7 @@ __global__ void __launch_bounds__(kRlcSortBlock) k_rlc_hist(RlcMsmArgs a) {
   const int g = blockIdx.x, w = blockIdx.y;
   for (int b = threadIdx.x; b < kRlcBuckets; b += kRlcSortBlock) hist[b] = 0;
   __syncthreads();
-  const int64_t np = a.p1 - a.p0, total = np + 2;
+  const int64_t np = a.p1 - a.p0, total = np + a.nextra;
   const int64_t t0 = (int64_t)g * a.chunk;
   const int64_t t1 = t0 + a.chunk < total ? t0 + a.chunk : total;
   const int16_t* dig = a.digits + (int64_t)w * a.dstride;
@@ -430,7 +519,7 @@ __global__ void __launch_bounds__(kRlcSortBlock) k_rlc_coarse(RlcMsmArgs a) {
     cnt[tid] = 0;
   }
   __syncthreads();
-  const int64_t total = (a.p1 - a.p0) + 2;
+  const int64_t total = (a.p1 - a.p0) + a.nextra;
   const int64_t c0 = (int64_t)g * a.chunk;
   const int64_t c1 = c0 + a.chunk < total ? c0 + a.chunk : total;
   const int16_t* dig = a.digits + (int64_t)w * a.dstride;
@@ -1043,6 +1132,21 @@ hipError_t launch_rlc_prepare(const RlcPrepArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+hipError_t launch_rlc_prepare_pairs(const RlcPrepArgs& a, hipStream_t st) {
+  if (!a.prod) return hipErrorInvalidValue;
+  // CPZ_RLC_PAIRS_WIDE=1 (measurement): four lanes per proof at every size
+  static const bool wide_all = [] {
+    const char* v = getenv("CPZ_RLC_PAIRS_WIDE");
+    return v && v[0] == '1';
+  }();
+  if (a.n <= kRlcPrepWideMax || wide_all)
+    hipLaunchKernelGGL(k_rlc_prepare4_pairs, dim3((unsigned)((a.n + 63) / 64)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_rlc_prepare_pairs, dim3((unsigned)((a.n + kRlcPrepBlock - 1) / kRlcPrepBlock)),
+                       dim3(kRlcPrepBlock), 0, st, a);
+  return hipGetLastError();
+}
+
 void rlc_sort_geometry(RlcMsmArgs& a, int64_t npts) {
   int64_t g = (npts + kRlcSortChunk - 1) / kRlcSortChunk;
   if (g > kRlcSortGroups) g = kRlcSortGroups;
@@ -1060,11 +1164,18 @@ void rlc_sort_geometry(RlcMsmArgs& a, int64_t npts) {
 }
 
 hipError_t launch_rlc_msm(const RlcMsmArgs& a, const sc* block_sums, int64_t b0, int64_t b1, const ge_niels* tab,
-                          hipStream_t st, hipEvent_t* marks, hipEvent_t final_wait, hipEvent_t final_done) {
+                          hipStream_t st, hipEvent_t* marks, hipEvent_t final_wait, hipEvent_t final_done,
+                          const RlcPairExtra* px) {
   hipError_t e;
   auto mark = [&](int k) -> hipError_t { return marks ? hipEventRecord(marks[k], st) : hipSuccess; };
   if ((e = mark(0)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_rlc_extra, dim3(1), dim3(256), 0, st, a, block_sums, b0, b1, tab);
+  if (px) {
+    if (px->npairs <= 0 || a.nextra != 2 * px->npairs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rlc_extra_pairs, dim3((unsigned)px->npairs), dim3(256), 0, st, a, *px);
+  } else {
+    if (a.nextra != 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rlc_extra, dim3(1), dim3(256), 0, st, a, block_sums, b0, b1, tab);
+  }
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const size_t lds = sizeof(uint32_t) * kRlcBuckets;  // 128 KB of the 160 KB LDS
   // The attribute is per device: one bit per ordinal (contexts on several GPUs launch from
@@ -1091,13 +1202,14 @@ hipError_t launch_rlc_msm(const RlcMsmArgs& a, const sc* block_sums, int64_t b0,
   hipLaunchKernelGGL(k_rlc_fine, dim3(kRlcCoarse, kRlcWindows), dim3(kRlcSortBlock), 0, st, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = mark(1)) != hipSuccess) return e;
-  const int64_t chunks = ((a.p1 - a.p0) + 2 + a.echunk - 1) / a.echunk;  // per window: entries <= points
+  const int64_t npts = (a.p1 - a.p0) + a.nextra;
+  const int64_t chunks = (npts + a.echunk - 1) / a.echunk;  // per window: entries <= points
   hipLaunchKernelGGL(k_rlc_bucket, dim3((unsigned)((chunks + 255) / 256), kRlcWindows), dim3(256), 0, st, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = mark(2)) != hipSuccess) return e;
   RlcMsmArgs a2 = a;
-  a2.sparse = CPZ_RLC_SPARSE && (a.p1 - a.p0) + 2 <= kRlcSparsePts ? 1 : 0;
-  a2.sgroups = (int)std::min<int64_t>(kRlcSparseMaxGroups, std::max<int64_t>(4, ((a.p1 - a.p0) + 2 + 127) / 128));
+  a2.sparse = CPZ_RLC_SPARSE && npts <= kRlcSparsePts ? 1 : 0;
+  a2.sgroups = (int)std::min<int64_t>(kRlcSparseMaxGroups, std::max<int64_t>(4, (npts + 127) / 128));
   hipLaunchKernelGGL(k_rlc_bucket_fix, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, a2);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = mark(3)) != hipSuccess) return e;

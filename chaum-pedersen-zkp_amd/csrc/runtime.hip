@@ -148,9 +148,10 @@ bool is_no_partial(const uint8_t p[32]) {
 //                Capacity: proofs of one MSM (a span of at most CPZ_RLC_SPAN proofs).
 struct RlcPrepared {
   DevBuf pts, dig, bsum, qsum;
+  DevBuf prod;  // mixed-pair batch checks only: 2 x 32 B per proof, a s and b s (RlcPrepArgs::prod)
   int64_t cap = 0;
   void release() {
-    for (DevBuf* b : {&pts, &dig, &bsum, &qsum}) b->release();
+    for (DevBuf* b : {&pts, &dig, &bsum, &qsum, &prod}) b->release();
     cap = 0;
   }
 };
@@ -256,6 +257,10 @@ struct cpz_ctx {
   hipStream_t span_stream = nullptr;
   hipEvent_t span_ev[3] = {nullptr, nullptr, nullptr};
   DevBuf rl_flags, rl_parts;
+  // mixed-pair batch check (cpz_verify_batch_pairs): the call's pairs' encodings, what
+  // k_pair_setup leaves per pair, their Niels points, and -- once a failing batch reaches its
+  // first leaf -- the descriptor table with the resident sets' tables
+  DevBuf bp_gh, bp_setup, bp_pts, bp_desc;
   // partitioned batch check (part.hip): sorted lists / offsets / window sums of one chunk of
   // blocks, every block's partial and fail flag, the sum's scratch, the failing-block list
   DevBuf pt_lists, pt_offs, pt_wsum, pt_part, pt_fail, pt_tmp, pt_blocks, pt_assign;
@@ -1044,11 +1049,15 @@ int batch_challenges(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, con
 
 // Decode + weights + points/digits of the whole batch (after batch_challenges).
 // need_msm = false (the partitioned check): the span-sized MSM set is not reserved.
+// pair_room > 0 (a mixed-pair batch, challenges from k_challenge_pairs): both sets are reserved
+// for that many proofs more -- the room of the pairs' extra points -- and the prepare writes every
+// proof's products a s and b s (RlcPrepared::prod) instead of the block sums.
 int rlc_prepare_points(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, const void* r1, const void* r2,
                        const void* s, uint8_t* status, const uint8_t seed[32], uint64_t first_index, hipStream_t st,
-                       bool need_msm = true) {
-  int rc = need_msm ? rlc_reserve(ctx, (int64_t)n) : rlc_reserve_prepared(ctx->rl_prep, (int64_t)n);
+                       bool need_msm = true, int64_t pair_room = 0) {
+  int rc = need_msm ? rlc_reserve(ctx, (int64_t)n + pair_room) : rlc_reserve_prepared(ctx->rl_prep, (int64_t)n);
   if (rc) return rc;
+  if (pair_room) CPZ_HIP(ctx->rl_prep.prod.ensure((size_t)ctx->rl_prep.cap * 2 * sizeof(cpz::sc)));
   CPZ_HIP(ctx->rl_flags.ensure(4 * sizeof(int)));
   cpz::RlcPrepArgs pa;
   pa.n = (int64_t)n;
@@ -1068,6 +1077,7 @@ int rlc_prepare_points(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, c
   pa.quarter_sums = static_cast<cpz::sc*>(ctx->rl_prep.qsum.p);
   pa.eq_only = ctx->call_eq ? 1 : 0;
   pa.any_bad = static_cast<int*>(ctx->rl_flags.p) + 3;
+  if (pair_room) pa.prod = static_cast<cpz::sc*>(ctx->rl_prep.prod.p);
   CPZ_HIP(hipMemsetAsync(pa.any_bad, 0, sizeof(int), st));
 #if defined(CPZ_CLOCK_PROBE)
   ctx->clk_waves[0] = (size_t)((n + cpz::kRlcPrepBlock - 1) / cpz::kRlcPrepBlock) * (cpz::kRlcPrepBlock / 64);
@@ -1077,7 +1087,7 @@ int rlc_prepare_points(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, c
 #endif
   {
     StageTimer t(ctx, 2, st);
-    CPZ_HIP(cpz::launch_rlc_prepare(pa, st));
+    CPZ_HIP(pair_room ? cpz::launch_rlc_prepare_pairs(pa, st) : cpz::launch_rlc_prepare(pa, st));
   }
   return CPZ_OK;
 }
@@ -2138,6 +2148,7 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
     b->release();
   ctx->rl_flags.release();
   ctx->rl_parts.release();
+  for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc}) b->release();
 #if defined(CPZ_CLOCK_PROBE)
   for (DevBuf& b : ctx->clk) b.release();
 #endif
@@ -2398,6 +2409,304 @@ int cpz_verify_each_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const 
   CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
   CPZ_HIP(hipStreamSynchronize(ctx->stream));
   if (pinned) std::memcpy(status_out, dst, n);
+  return CPZ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- mixed-pair RLC batch check (cpz_verify_batch_pairs) -----------------------------------
+// Proofs of room both RLC sets are reserved beyond the batch: the 2 CPZ_PAIRS_MAX extra points
+// (g_p, h_p per pair) take the last 4 kPairRoom point slots and digit columns of the prepared
+// set, and the MSM set's sorted-entry rows and heads hold them as points of the MSM.
+constexpr int64_t kPairRoom = (2 * CPZ_PAIRS_MAX + 3) / 4;
+static_assert(4ll * (CPZ_BATCH_PAIRS_MAX_PROOFS + kPairRoom) + 2 <= cpz::kRlcMaxMsmPoints,
+              "a mixed-pair MSM exceeds the sort-entry format");
+static_assert(CPZ_BATCH_PAIRS_MAX_PROOFS + kPairRoom <= CPZ_RLC_SPAN, "a mixed-pair batch is one MSM span");
+
+// One mixed-pair batch in progress: its staged rows and contexts, the table-less descriptors
+// and indices on the device, and what the fallback needs to make the pairs resident.
+struct PairBatch {
+  size_t npairs = 0;
+  int64_t n = 0;
+  const uint8_t* pairs = nullptr;         // host: npairs x (g, h)
+  const uint32_t* pair_idx = nullptr;     // host
+  const void* rows[5] = {};               // device: y1, y2, r1, r2, s
+  const void* cb = nullptr;               // device contexts (stage_inputs)
+  const uint64_t* co = nullptr;
+  const uint8_t* cp = nullptr;
+  const uint32_t* d_idx = nullptr;        // device: n indices
+  uint8_t* d_status = nullptr;
+  const cpz::PairDesc* d_full = nullptr;  // device descriptors with tables, set at the first leaf
+};
+
+// The MSM over proofs [lo, hi) (lo a multiple of kRlcPrepBlock) of the prepared mixed-pair batch:
+// k_rlc_extra_pairs' 2 npairs points, then the sort and reduction of any MSM.
+int pairs_range_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
+  cpz::RlcMsmArgs m;
+  if (int rc = rlc_msm_args(ctx->rl_prep, ctx->rl_msm, lo, hi, m)) return rc;
+  if (ctx->rl_prep.cap < b.n + kPairRoom || ctx->rl_msm.cap < (hi - lo) + kPairRoom)
+    return fail(CPZ_EINVAL, "internal: RLC sets reserved without room for the pairs' points");
+  m.e0 = 4 * (ctx->rl_prep.cap - kPairRoom);
+  m.nextra = 2 * (int)b.npairs;
+  cpz::rlc_sort_geometry(m, (m.p1 - m.p0) + m.nextra);
+  cpz::RlcPairExtra px;
+  px.prod = static_cast<const cpz::sc*>(ctx->rl_prep.prod.p);
+  px.pair_idx = b.d_idx;
+  px.lo = lo;
+  px.hi = hi;
+  px.gh = static_cast<const cpz::ge_niels*>(ctx->bp_pts.p);
+  px.npairs = (int)b.npairs;
+  StageTimer t(ctx, 3, st);
+  CPZ_HIP(cpz::launch_rlc_msm(m, nullptr, 0, 0, nullptr, st, nullptr, nullptr, nullptr, &px));
+  return CPZ_OK;
+}
+
+// Per-proof verification of [lo, hi) under every entry's own pair, on the rows already on the
+// device: the mixed-pair latency kernels in pieces of at most CPZ_PAIRS_MAX_PROOFS.  The first
+// leaf makes the call's pairs resident (light sets unless a full one is cached).
+int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
+  if (!b.d_full) {
+    std::vector<cpz::PairDesc> full(b.npairs);
+    for (size_t p = 0; p < b.npairs; p++) {
+      int rc = ensure_generators(ctx, b.pairs + 64 * p, b.pairs + 64 * p + 32, false, true);
+      if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
+      pair_desc(full[p], *ctx->gs);
+    }
+    CPZ_HIP(ctx->bp_desc.ensure(full.size() * sizeof(cpz::PairDesc)));
+    CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, full.data(), full.size() * sizeof(cpz::PairDesc), hipMemcpyHostToDevice, st));
+    CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `full` goes
+    b.d_full = static_cast<const cpz::PairDesc*>(ctx->bp_desc.p);
+  }
+  ctx->fb_stats[4] += (uint64_t)(hi - lo);
+  for (int64_t a = lo; a < hi; a += CPZ_PAIRS_MAX_PROOFS) {
+    const int64_t m = std::min<int64_t>(hi - a, CPZ_PAIRS_MAX_PROOFS);
+    cpz::ChallengeArgs ca{};
+    ca.eq_only = ctx->call_eq ? 1 : 0;
+    ca.n = m;
+    ca.y1 = static_cast<const uint32_t*>(b.rows[0]) + 8 * a;
+    ca.y2 = static_cast<const uint32_t*>(b.rows[1]) + 8 * a;
+    ca.r1 = static_cast<const uint32_t*>(b.rows[2]) + 8 * a;
+    ca.r2 = static_cast<const uint32_t*>(b.rows[3]) + 8 * a;
+    ca.s = static_cast<const uint32_t*>(b.rows[4]) + 8 * a;
+    ca.ctx_bytes = static_cast<const uint8_t*>(b.cb);
+    ca.ctx_off = b.co ? b.co + a : nullptr;  // absolute offsets into ctx_bytes
+    ca.ctx_present = b.cp ? b.cp + a : nullptr;
+    ca.prefix = nullptr;  // per pair: PairDesc
+    ca.c_out = nullptr;
+    ca.status_out = b.d_status + a;
+    cpz::VerifyArgs va{};
+    va.n = m;
+    va.y1 = ca.y1;
+    va.y2 = ca.y2;
+    va.r1 = ca.r1;
+    va.r2 = ca.r2;
+    va.s = ca.s;
+    va.c = nullptr;  // computed in the kernel
+    va.status = b.d_status + a;
+    va.comb = nullptr;
+    va.eq_only = ca.eq_only;
+    cpz::PairArgs pa;
+    pa.desc = b.d_full;
+    pa.pair_idx = b.d_idx + a;
+    if (int rc = launch_verify_chunks(ctx, va, 4, st, nullptr, true, &ca, &pa)) return rc;
+  }
+  return CPZ_OK;
+}
+
+// rlc_fallback for a mixed-pair batch: the same fan-out-8 bisection aligned to kRlcPrepBlock, each
+// part's partial one more MSM over the prepared points with that part's per-pair extras.
+int pairs_fallback(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st, int depth) {
+  if (hi - lo <= (int64_t)CPZ_PAIRS_MAX_PROOFS || depth > 12) return pairs_leaf(ctx, b, lo, hi, st);
+  int64_t cuts[kFanout + 1];
+  for (int k = 0; k <= kFanout; k++) {
+    int64_t c = lo + ((hi - lo) * k) / kFanout;
+    c = (c / cpz::kRlcPrepBlock) * cpz::kRlcPrepBlock;
+    cuts[k] = k == 0 ? lo : (k == kFanout ? hi : (c < lo ? lo : c));
+  }
+  bool failing[kFanout];
+  int nfail = 0;
+  for (int k = 0; k < kFanout; k++) {
+    failing[k] = false;
+    if (cuts[k + 1] <= cuts[k]) continue;
+    if (int rc = pairs_range_launch(ctx, b, cuts[k], cuts[k + 1], st)) return rc;
+    int ident = 0;
+    CPZ_HIP(hipMemcpyAsync(&ident, ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+    ctx->fb_stats[5] += 1;
+    failing[k] = !ident;
+    nfail += failing[k] ? 1 : 0;
+  }
+  if (2 * nfail > kFanout) return pairs_leaf(ctx, b, lo, hi, st);  // dense failures: no pruning left
+  for (int k = 0; k < kFanout; k++) {
+    if (!failing[k]) continue;
+    if (int rc = pairs_fallback(ctx, b, cuts[k], cuts[k + 1], st, depth + 1)) return rc;
+  }
+  return CPZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpz_verify_batch_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const uint32_t* pair_idx,
+                           const uint8_t* y1, const uint8_t* y2, const uint8_t* r1, const uint8_t* r2, const uint8_t* s,
+                           const uint8_t* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present,
+                           const uint8_t seed[32], uint64_t first_index, uint8_t partial_out[32], int* batch_ok,
+                           uint8_t* status_out) {
+  return cpz_verify_batch_pairs_ex(ctx, 0, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, ctx_bytes, ctx_off,
+                                   ctx_present, seed, first_index, partial_out, batch_ok, status_out);
+}
+
+int cpz_verify_batch_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
+                              const uint32_t* pair_idx, const uint8_t* y1, const uint8_t* y2, const uint8_t* r1,
+                              const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                              const uint8_t* ctx_present, const uint8_t seed[32], uint64_t first_index,
+                              uint8_t partial_out[32], int* batch_ok, uint8_t* status_out) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
+  if (npairs > CPZ_PAIRS_MAX)
+    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
+                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (n > CPZ_BATCH_PAIRS_MAX_PROOFS)
+    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_BATCH_PAIRS_MAX_PROOFS (" +
+                                std::to_string(CPZ_BATCH_PAIRS_MAX_PROOFS) + ")");
+  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !seed || !partial_out || !batch_ok)
+    return fail(CPZ_EINVAL, "null input pointer");
+  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  // the kernels trust the indices: checked here, before anything is staged
+  for (size_t i = 0; i < n; i++)
+    if (pair_idx[i] >= npairs)
+      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
+                                  " is not below npairs (" + std::to_string(npairs) + ")");
+  // Parameters::with_generators (gadgets.rs:77-103) for every pair
+  static const uint8_t zero[32] = {0};
+  for (size_t p = 0; p < npairs; p++) {
+    const uint8_t *g = pairs + 64 * p, *h = g + 32;
+    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
+    if (std::memcmp(g, h, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
+  }
+  if (npairs == 1)
+    return cpz_verify_batch_ex(ctx, flags, pairs, pairs + 32, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present,
+                               seed, first_index, partial_out, batch_ok, status_out);
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  for (auto& v : ctx->fb_stats) v = 0;
+  hipStream_t st = ctx->stream;
+  int rc = order_after_last(ctx, st);
+  if (rc) return rc;
+  // Per-pair set-up, no table: one launch for the snapshots and the pairs' Niels points, one
+  // copy back for the snapshots and decode flags (timed inside stage 2).
+  CPZ_HIP(ctx->bp_gh.ensure(npairs * 64));
+  CPZ_HIP(ctx->bp_setup.ensure(npairs * sizeof(cpz::PairSetup)));
+  CPZ_HIP(ctx->bp_pts.ensure(2 * npairs * sizeof(cpz::ge_niels)));
+  std::vector<cpz::PairSetup> setup(npairs);
+  {
+    StageTimer t(ctx, 2, st);
+    CPZ_HIP(hipMemcpyAsync(ctx->bp_gh.p, pairs, npairs * 64, hipMemcpyHostToDevice, st));
+    CPZ_HIP(cpz::launch_pair_setup(static_cast<const uint32_t*>(ctx->bp_gh.p), (int)npairs,
+                                   static_cast<cpz::PairSetup*>(ctx->bp_setup.p),
+                                   static_cast<cpz::ge_niels*>(ctx->bp_pts.p), st));
+    CPZ_HIP(hipMemcpyAsync(setup.data(), ctx->bp_setup.p, npairs * sizeof(cpz::PairSetup), hipMemcpyDeviceToHost, st));
+  }
+  CPZ_HIP(hipStreamSynchronize(st));
+  for (size_t p = 0; p < npairs; p++)
+    if (!setup[p].ok[0] || !setup[p].ok[1])
+      return fail(CPZ_EGENERATOR,
+                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
+  // The descriptors (null tables) with the host-derived fixed-schedule masks, and the indices,
+  // go to the device in one block with the rows (stage_inputs' extra).
+  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
+  {
+    uint32_t k1[50], k2[50];
+    const bool masks = cpz::challenge_masks(k1, k2);
+    for (size_t p = 0; p < npairs; p++) {
+      cpz::PairDesc d{};
+      std::memcpy(d.prefix, setup[p].prefix, sizeof(d.prefix));
+      words_from_bytes(d.gh_words, pairs + 64 * p, pairs + 64 * p + 32);
+      d.fast_noctx = masks && cpz::challenge_prefix_is_fixed(d.prefix[1]) ? 1 : 0;
+      std::memcpy(d.k1, k1, sizeof(d.k1));
+      std::memcpy(d.k2, k2, sizeof(d.k2));
+      d.fast_ctx32 = cpz::challenge_prefix_is_ctx32(d.prefix[0]) &&
+                             cpz::challenge_masks_ctx32(d.c32, d.gh_words, d.gh_words + 8)
+                         ? 1
+                         : 0;
+      std::memcpy(extra.data() + p * sizeof(cpz::PairDesc), &d, sizeof(d));
+    }
+  }
+  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  const uint8_t* host[5] = {y1, y2, r1, r2, s};
+  const void* dev[5];
+  const void* dcb;
+  const uint64_t* dco;
+  const uint8_t* dcp;
+  const void* dex = nullptr;
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, false, nullptr, nullptr,
+                    extra.data(), extra.size(), &dex);
+  if (rc) return rc;
+  if (!dex) return fail(CPZ_EHIP, "internal: the pair descriptors were not staged");
+  CPZ_HIP(ctx->st.ensure(n));
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  PairBatch b;
+  b.npairs = npairs;
+  b.n = (int64_t)n;
+  b.pairs = pairs;
+  b.pair_idx = pair_idx;
+  for (int k = 0; k < 5; k++) b.rows[k] = dev[k];
+  b.cb = dcb;
+  b.co = dco;
+  b.cp = dcp;
+  b.d_idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(dex) + npairs * sizeof(cpz::PairDesc));
+  b.d_status = static_cast<uint8_t*>(ctx->st.p);
+  {
+    cpz::ChallengeArgs ca{};
+    ca.eq_only = ctx->call_eq ? 1 : 0;
+    ca.n = (int64_t)n;
+    ca.y1 = static_cast<const uint32_t*>(dev[0]);
+    ca.y2 = static_cast<const uint32_t*>(dev[1]);
+    ca.r1 = static_cast<const uint32_t*>(dev[2]);
+    ca.r2 = static_cast<const uint32_t*>(dev[3]);
+    ca.s = static_cast<const uint32_t*>(dev[4]);
+    ca.ctx_bytes = static_cast<const uint8_t*>(dcb);
+    ca.ctx_off = dco;
+    ca.ctx_present = dcp;
+    ca.prefix = nullptr;  // per pair: PairDesc
+    ca.c_out = static_cast<uint32_t*>(ctx->c.p);
+    ca.status_out = b.d_status;
+    cpz::PairArgs pa;
+    pa.desc = static_cast<const cpz::PairDesc*>(dex);
+    pa.pair_idx = b.d_idx;
+    StageTimer t(ctx, 0, st);
+    CPZ_HIP(cpz::launch_challenge_pairs(ca, pa, st));
+  }
+  if ((rc = rlc_prepare_points(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], b.d_status, seed, first_index, st, true,
+                               kPairRoom)))
+    return rc;
+  if ((rc = pairs_range_launch(ctx, b, 0, (int64_t)n, st))) return rc;
+  // the partial, its identity flag, the any-bad word and the statuses with one synchronisation;
+  // the caller's buffers are written only once nothing can fail before the fallback
+  uint8_t part[32];
+  int words[2] = {0, 0};
+  std::vector<uint8_t> st_host(status_out ? n : 0);
+  CPZ_HIP(hipMemcpyAsync(part, ctx->rl_msm.partial.p, 32, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipMemcpyAsync(&words[0], ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipMemcpyAsync(&words[1], static_cast<int*>(ctx->rl_flags.p) + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (status_out) CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  const bool ident = words[0] != 0;
+  if (!ident && status_out) {
+    ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
+    if ((rc = pairs_fallback(ctx, b, 0, (int64_t)n, st, 0))) return rc;
+    CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+  }
+  std::memcpy(partial_out, part, 32);
+  *batch_ok = (ident && words[1] == 0) ? 1 : 0;
+  if (status_out) std::memcpy(status_out, st_host.data(), n);
   return CPZ_OK;
 }
 

@@ -246,6 +246,49 @@ int cpz_verify_batch_device(cpz_ctx *ctx, const uint8_t g[32], const uint8_t h[3
                             uint8_t partial_out[32], int *batch_ok, void *d_status_out, int fallback,
                             void *stream);
 
+/* The same batch check over entries that carry their own generators, in one MSM: `pairs` and
+ * pair_idx mean what they mean for cpz_verify_each_pairs (npairs rows of g then h, at most
+ * CPZ_PAIRS_MAX; rows may repeat and may be the default pair).  Entry i is weighted by the
+ * (first_index + i)-th weights of `seed` and takes the challenge of its own pair's transcript:
+ *   P = sum_i [a_i s_i] g_p(i) - [a_i] r1_i - [a_i c_i] y1_i + [b_i s_i] h_p(i) - [b_i] r2_i - [b_i c_i] y2_i
+ * -- the sum over the pairs of cpz_verify_batch's partial over that pair's entries, weights keyed
+ * by the entries' positions in this call.  The MSM sees g_p and h_p as 2 npairs more points with
+ * the per-pair sums of a_i s_i and b_i s_i as scalars, so a batch that passes builds no table
+ * and no comb, whatever its pairs: only a failing batch with status_out makes its pairs resident
+ * (light sets, stage 13), when its bisection reaches the first range of at most
+ * CPZ_PAIRS_MAX_PROOFS entries, which the mixed-pair per-proof kernels verify.  With every pair's
+ * tables already resident and n <= CPZ_PAIRS_MAX_PROOFS, cpz_verify_each_pairs is the faster call
+ * (one launch); this one is for pairs the context has not seen, or too many to keep, and for
+ * larger n.
+ *   partial_out, batch_ok   as for cpz_verify_batch (both required); shards with global
+ *                first_index values combine (cpz_combine_partials) to the unsharded P.
+ *   status_out   optional (n).  Entries with a non-zero decode-level status carry zero weight and
+ *                report it; when the batch fails, every status is what cpz_verify_each_pairs_ex
+ *                reports for that entry.  The fallback is the bisection alone (the density probe
+ *                and the partitioned check serve one pair), hence CPZ_BATCH_PAIRS_MAX_PROOFS.
+ *   seed         secret and unpredictable, as for cpz_verify_batch.
+ * CPZ_CALL_EQUATIONS_ONLY and the context's commitment-check mode apply as for cpz_verify_batch;
+ * cpz_ctx_fallback_stats reports CPZ_FALLBACK_NONE or _BISECTION with out[4] and out[5].
+ * npairs == 1 is cpz_verify_batch_ex under that pair.  Checked before anything is staged,
+ * cpz_last_error naming the pair or the entry, and no output buffer is written on an error:
+ * n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_PAIRS_MAX, n > CPZ_BATCH_PAIRS_MAX_PROOFS, a
+ * null pointer (status_out and the contexts excepted) or a pair_idx[i] >= npairs -> CPZ_EINVAL; a
+ * pair that is the identity, has g == h or does not decode -> CPZ_EGENERATOR.  Host buffers
+ * only: the indices are checked on the host and the kernels trust them. */
+#define CPZ_BATCH_PAIRS_MAX_PROOFS 1048576 /* 1 << 20 */
+int cpz_verify_batch_pairs(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
+                           const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                           const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                           const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                           const uint8_t *ctx_present, const uint8_t seed[32], uint64_t first_index,
+                           uint8_t partial_out[32], int *batch_ok, uint8_t *status_out);
+int cpz_verify_batch_pairs_ex(cpz_ctx *ctx, uint32_t flags, size_t npairs, const uint8_t *pairs, size_t n,
+                              const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                              const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                              const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                              const uint8_t *ctx_present, const uint8_t seed[32], uint64_t first_index,
+                              uint8_t partial_out[32], int *batch_ok, uint8_t *status_out);
+
 /* What the last cpz_verify_batch[_device] call on the context did to locate invalid entries
  * (fallback != 0), for tests and benchmarks:
  *   out[0]  path: CPZ_FALLBACK_NONE (the batch passed, or no fallback), _BISECTION (sub-range

@@ -249,6 +249,38 @@ impl Gpu {
         Ok(st)
     }
 
+    /// The batch check over entries that carry their own generators, in one MSM
+    /// (`cpz_verify_batch_pairs_ex`): entry i stands under `pairs[pair_idx[i]]`, at most
+    /// `CPZ_PAIRS_MAX` pairs and `CPZ_BATCH_PAIRS_MAX_PROOFS` entries.  Returns (partial encoding,
+    /// batch_ok, statuses) as `verify_batch_with`; a batch that passes builds no table for any
+    /// pair, and a failing one reports what `verify_each_pairs` returns for every entry.
+    pub fn verify_batch_pairs(&self, flags: CallFlags, pairs: &[(Bytes32, Bytes32)], pair_idx: &[u32],
+                              entries: &[Entry<'_>], seed: &Bytes32, first_index: u64)
+                              -> Result<(Bytes32, bool, Vec<u8>), GpuError> {
+        if pair_idx.len() != entries.len() {
+            return Err(GpuError { code: sys::CPZ_EINVAL, message: "pair_idx must hold one index per entry".into() });
+        }
+        let mut gh = Vec::with_capacity(64 * pairs.len());
+        for (g, h) in pairs {
+            gh.extend_from_slice(g);
+            gh.extend_from_slice(h);
+        }
+        let soa = Soa::new(entries);
+        let (cb, co, cp) = soa.ctx_ptrs();
+        let mut partial = [0u8; 32];
+        let mut ok: c_int = 0;
+        let mut st = vec![0u8; entries.len()];
+        let r = &soa.rows;
+        // SAFETY: as verify_each_pairs; seed and partial hold 32 bytes, ok is a local.
+        check(unsafe {
+            sys::cpz_verify_batch_pairs_ex(self.ctx, flags, pairs.len(), gh.as_ptr(), entries.len(), pair_idx.as_ptr(),
+                                           r[0].as_ptr(), r[1].as_ptr(), r[2].as_ptr(), r[3].as_ptr(), r[4].as_ptr(),
+                                           cb, co, cp, seed.as_ptr(), first_index, partial.as_mut_ptr(), &mut ok,
+                                           st.as_mut_ptr())
+        })?;
+        Ok((partial, ok != 0, st))
+    }
+
     /// `Verifier::verify_response` (verifier/mod.rs:144-171) with caller challenges.
     pub fn verify_response(&self, g: &Bytes32, h: &Bytes32, entries: &[Entry<'_>], challenges: &[Bytes32])
                            -> Result<Vec<u8>, GpuError> {
