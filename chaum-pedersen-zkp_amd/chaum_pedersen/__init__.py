@@ -407,6 +407,25 @@ class Gpu:
             _ptr(off), _ptr(present), _ptr(out)))
         return out
 
+    def verify_each_pairs_bulk(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, contexts=None,
+                               equations_only: bool = False) -> np.ndarray:
+        """verify_each_pairs without its bound on the proofs (cpz_verify_each_pairs_bulk_ex): at
+        most PAIRS_MAX pairs and PAIRS_BULK_MAX_PROOFS proofs, the same statuses.  Up to
+        PAIRS_MAX_PROOFS proofs it is verify_each_pairs; above, the proofs are verified in chunks
+        of at most 16384 on eight lanes per proof, each from its own pair's tables.  pair_idx: n
+        integers in [0, len(pairs)), checked here before the library is called."""
+        n = len(y1)
+        npairs = len(pairs)
+        idx = _pair_indices(pair_idx, n, npairs)
+        arrs = [_rows(a, n, nm) for a, nm in ((y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2"), (s, "s"))]
+        gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+        blob, off, present = _ctx_arrays(contexts, n)
+        out = np.empty(n, dtype=np.uint8)
+        _native.check(self._lib.cpz_verify_each_pairs_bulk_ex(
+            self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
+            _ptr(off), _ptr(present), _ptr(out)))
+        return out
+
     def challenges(self, y1, y2, r1, r2, contexts=None, params: Optional[Parameters] = None) -> np.ndarray:
         params = params or Parameters()
         n = len(y1)
@@ -574,6 +593,31 @@ class Gpu:
         _native.check(self._lib.cpz_verify_each_device(
             self._h, params.g, params.h, n, dp(y1), dp(y2), dp(r1), dp(r2), dp(s), dp(ctx_bytes), dp(ctx_off),
             dp(ctx_present), dp(status_out), _torch_stream(stream)))
+
+    def verify_each_pairs_device(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, status_out,
+                                 stream: Optional[int] = None, ctx_bytes=None, ctx_off=None, ctx_present=None,
+                                 equations_only: bool = False) -> None:
+        """verify_each_pairs_bulk on device tensors (cpz_verify_each_pairs_device): rows uint8
+        (n, 32), 16-B aligned; pair_idx an int32 or uint32 device tensor of n elements, whose values
+        the library checks on the device before any kernel follows them (an index outside
+        [0, len(pairs)) raises CpzError with CPZ_EINVAL and leaves status_out untouched).  Returns
+        with `stream` synchronised and status_out filled."""
+        n = int(y1.shape[0])
+        dtype = str(getattr(pair_idx, "dtype", None))
+        if not hasattr(pair_idx, "data_ptr") or dtype not in ("torch.int32", "torch.uint32"):
+            raise InvalidParams("pair_idx must be an int32 or uint32 device tensor, not %s (%s)"
+                                % (type(pair_idx).__name__, dtype))
+        if pair_idx.dim() != 1 or int(pair_idx.numel()) != n or not pair_idx.is_contiguous():
+            raise InvalidParams("pair_idx must hold one index per proof: shape %s for %d proofs"
+                                % (tuple(pair_idx.shape), n))
+        if not pair_idx.is_cuda:
+            raise InvalidParams("pair_idx must be a device tensor (it is on %s)" % pair_idx.device)
+        npairs = len(pairs)
+        gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+        dp = lambda t: None if t is None else t.data_ptr()
+        _native.check(self._lib.cpz_verify_each_pairs_device(
+            self._h, _flags(equations_only), npairs, _ptr(gh), n, dp(pair_idx), dp(y1), dp(y2), dp(r1), dp(r2), dp(s),
+            dp(ctx_bytes), dp(ctx_off), dp(ctx_present), dp(status_out), _torch_stream(stream)))
 
     def verify_response_device(self, y1, y2, r1, r2, s, c, status_out, params: Optional[Parameters] = None,
                                stream: Optional[int] = None) -> None:

@@ -36,10 +36,12 @@ EXPORTED = (
     "cpz_abi_version", "cpz_ctx_set_commitment_checks", "cpz_ctx_stage_times_n", "cpz_ctx_fallback_stats",
     "cpz_verify_each_ex", "cpz_verify_batch_ex", "cpz_verify_response_ex",
     "cpz_verify_each_pairs", "cpz_verify_each_pairs_ex", "cpz_verify_batch_pairs", "cpz_verify_batch_pairs_ex",
+    "cpz_verify_each_pairs_bulk", "cpz_verify_each_pairs_bulk_ex", "cpz_verify_each_pairs_device",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
 BATCH_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_BATCH_PAIRS_MAX_PROOFS: proofs per cpz_verify_batch_pairs call
+PAIRS_BULK_MAX_PROOFS = 1 << 20    # CPZ_PAIRS_BULK_MAX_PROOFS: proofs per cpz_verify_each_pairs_bulk / _device call
 CALL_EQUATIONS_ONLY = 1   # CPZ_CALL_EQUATIONS_ONLY: commitment checks off for one call
 NUM_STAGES = 16
 FALLBACK_STATS = 8
@@ -80,6 +82,15 @@ def _declare(lib):
     lib.cpz_verify_each_pairs_ex.restype = ctypes.c_int
     lib.cpz_verify_each_pairs_ex.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] + [_p] * 5 +
                                              [_p, _p, _p, _p])
+    lib.cpz_verify_each_pairs_bulk.restype = ctypes.c_int
+    lib.cpz_verify_each_pairs_bulk.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p] + [_p] * 5 +
+                                               [_p, _p, _p, _p])
+    lib.cpz_verify_each_pairs_bulk_ex.restype = ctypes.c_int
+    lib.cpz_verify_each_pairs_bulk_ex.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] +
+                                                  [_p] * 5 + [_p, _p, _p, _p])
+    lib.cpz_verify_each_pairs_device.restype = ctypes.c_int
+    lib.cpz_verify_each_pairs_device.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] +
+                                                 [_p] * 5 + [_p, _p, _p, _p, _p])
     lib.cpz_verify_each_device.restype = ctypes.c_int
     lib.cpz_verify_each_device.argtypes = [_p, _p, _p, ctypes.c_size_t] + [_p] * 5 + [_p, _p, _p, _p, _p]
     lib.cpz_challenges.restype = ctypes.c_int

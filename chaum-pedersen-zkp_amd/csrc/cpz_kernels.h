@@ -177,7 +177,8 @@ struct VerifyArgs {
 // Mixed-pair calls (cpz_verify_each_pairs): proof i verifies under desc[pair_idx[i]] -- the
 // pair's Niels tables as variable bases (VerifyArgs::vtab / vtab16 of a single-pair call) and
 // what ChallengeArgs carries per (g, h): the two transcript prefixes, the generator words and
-// the fixed-schedule masks.  k_verify_wide_pairs / k_verify_small_pairs read these instead.
+// the fixed-schedule masks.  k_verify_wide_pairs / k_verify_small_pairs read these instead, and so
+// does the eight-lane kernel's mixed-pair arm (cpz_verify_each_pairs_bulk / _device, above 2048 proofs).
 struct PairDesc {
   const ge_niels* tab;           // GenSet::tab
   const int32_t* tab16;          // GenSet::tab16
@@ -191,7 +192,8 @@ struct PairDesc {
 };
 static_assert(sizeof(PairDesc) % 16 == 0, "descriptor rows stay 16-byte aligned");
 struct PairArgs {
-  const PairDesc* desc = nullptr;      // the call's pairs (host-checked: every index below is in range)
+  const PairDesc* desc = nullptr;      // the call's pairs (every index below is in range: checked on the
+                                       // host, or by k_pair_idx_check before any launch that reads them)
   const uint32_t* pair_idx = nullptr;  // n indices into desc
 };
 
@@ -252,6 +254,15 @@ hipError_t launch_verify_wide(const VerifyArgs& a, const ChallengeArgs& ca, hipS
 // prefix, gh_words and masks are unused, every proof takes its pair's variable-base tables.
 hipError_t launch_verify_small_pairs(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa, hipStream_t st);
 hipError_t launch_verify_wide_pairs(const VerifyArgs& a, const ChallengeArgs& ca, const PairArgs& pa, hipStream_t st);
+// The eight-lane kernel with a pair per proof (k_verify_quad_pairs): at most a.quad_max proofs,
+// a.c / a.status from launch_challenge_pairs, every proof's generator tables from its own pair's
+// descriptor as variable bases; a.comb / a.vtab / a.vtab16 are unused.  a.scratch as for
+// k_verify_quad (kQuadProofScratch bytes per proof).
+hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hipStream_t st);
+// Device-resident indices of a mixed-pair call against npairs: *first (set to kPairIdxOk by the
+// caller, on the same stream) ends as the lowest i with idx[i] >= npairs, or stays kPairIdxOk.
+constexpr uint32_t kPairIdxOk = 0xffffffffu;
+hipError_t launch_pair_idx_check(const uint32_t* idx, int64_t n, uint32_t npairs, uint32_t* first, hipStream_t st);
 int verify_each_blocks_per_cu();  // resident k_verify_each blocks per CU (occupancy API)
 hipError_t launch_prove_points(const ProveArgs& a, hipStream_t st);
 hipError_t launch_prove_response(const ProveArgs& a, hipStream_t st);

@@ -27,6 +27,8 @@
 // 3 non-canonical s, 4 identity commitment, 5 zero s.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "cpz_kernels.h"
 #include "ristretto.h"
 #include "scalar25519.h"
@@ -751,8 +753,15 @@ __device__ __forceinline__ ge_p3 p3_bcast(const ge_p3& P, int from) {
 // kVar: no comb for this (g, h) -- [s'] B comes from the Niels multiples 1..128 of B and
 // 2^128 B (a.vtab) as 2 x 16 signed radix-256 digits of s', one pair of mixed additions every
 // second window of the Straus loop (32 additions per equation against the comb's 16).
-template <bool kPre, bool kVar>
-__global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a) {
+// kPairs (k_verify_quad<false, true, true>): proof i takes those tables from its own pair's
+// descriptor, pa.desc[pa.pair_idx[i]].tab, instead of a.vtab -- a proof's eight lanes read one
+// descriptor, the four proofs of a wave and the 32 of a block generally different ones; a.comb,
+// a.vtab and a.vtab16 are unused.  The challenges (a.c) and response statuses (a.status) are
+// k_challenge_pairs'.  kPairs is a constant: the single-pair kernels compile without this arm.
+struct NoPairArgs {};
+template <bool kPre, bool kVar, bool kPairs = false>
+__global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditional_t<kPairs, PairArgs, NoPairArgs> pa) {
+  static_assert(!kPairs || (kVar && !kPre), "mixed pairs: variable bases, rows decoded here");
   const int t = threadIdx.x;
   int64_t i = (int64_t)blockIdx.x * 32 + (t >> 3);
   const int e = (t >> 2) & 1, q = t & 3;
@@ -821,8 +830,10 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a) {
   __threadfence_block();  // the quad's other lanes' fields (a negative digit reads them)
   CPZ_QUAD_STAMP(3);
   // Q = [u] Y' + [|v|] R' + [s'] B: identity (mod E[4]) iff the equation holds
-  const ge_niels* gt = kVar ? a.vtab + e * kNielsEntries : nullptr;          // B = g or h
-  const ge_niels* gt2 = kVar ? a.vtab + (2 + e) * kNielsEntries : nullptr;   // 2^128 B
+  const ge_niels* vt = kVar ? a.vtab : nullptr;
+  if constexpr (kPairs) vt = pa.desc[pa.pair_idx[i]].tab;
+  const ge_niels* gt = kVar ? vt + e * kNielsEntries : nullptr;          // B = g or h
+  const ge_niels* gt2 = kVar ? vt + (2 + e) * kNielsEntries : nullptr;   // 2^128 B
   ge_p3 acc = ge_identity();
 #pragma unroll 1
   for (int j = 0; j < 4; j++) {
@@ -904,6 +915,35 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a) {
     for (int k = 0; k < kQuadPhases; k++) a.clock_probe[k] = stamp[k];
 #endif
 #undef CPZ_QUAD_STAMP
+}
+
+// k_challenge_pairs' challenges and response statuses in a.c / a.status; at most a.quad_max
+// proofs (the slab holds kQuadProofScratch bytes of tables for each).
+hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (a.pre || a.blocks || !a.c || !a.status || !a.scratch || !pa.desc || !pa.pair_idx || a.n > a.quad_max)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_verify_quad<false, true, true>), dim3((unsigned)((a.n + 31) / 32)), dim3(256), 0, st, a, pa);
+  return hipGetLastError();
+}
+
+// The lowest i < n with idx[i] >= npairs into *first (kPairIdxOk when every index is in range;
+// the caller sets *first to that before the launch).  The device form of the mixed-pair call
+// reads the word back before it enqueues any kernel that follows idx[i] into the descriptors.
+__global__ void __launch_bounds__(256) k_pair_idx_check(const uint32_t* __restrict__ idx, int64_t n, uint32_t npairs,
+                                                        uint32_t* __restrict__ first) {
+  uint32_t low = kPairIdxOk;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    if (idx[i] >= npairs && (uint32_t)i < low) low = (uint32_t)i;
+  if (low != kPairIdxOk) atomicMin(first, low);
+}
+
+hipError_t launch_pair_idx_check(const uint32_t* idx, int64_t n, uint32_t npairs, uint32_t* first, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (!idx || !first || n >= (int64_t)kPairIdxOk) return hipErrorInvalidValue;
+  const int64_t blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  hipLaunchKernelGGL(k_pair_idx_check, dim3((unsigned)blocks), dim3(256), 0, st, idx, n, npairs, first);
+  return hipGetLastError();
 }
 
 
@@ -1087,15 +1127,15 @@ hipError_t launch_verify_each(const VerifyArgs& a, int grid, hipStream_t st) {
   const int64_t slots = a.blocks ? a.nblocks * (int64_t)a.block_proofs : a.n;
   if (a.vtab && (a.pre || slots > a.quad_max)) return hipErrorInvalidValue;  // no comb: eight-lane kernel only
   if (a.vtab) {
-    hipLaunchKernelGGL((k_verify_quad<false, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_verify_quad<false, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a, NoPairArgs{});
     return hipGetLastError();
   }
   if (CPZ_VERIFY_QUAD && slots <= a.quad_max) {  // small batches: eight lanes per proof
     const unsigned g = (unsigned)((slots + 31) / 32);
     if (a.pre)
-      hipLaunchKernelGGL((k_verify_quad<true, false>), dim3(g), dim3(256), 0, st, a);
+      hipLaunchKernelGGL((k_verify_quad<true, false>), dim3(g), dim3(256), 0, st, a, NoPairArgs{});
     else
-      hipLaunchKernelGGL((k_verify_quad<false, false>), dim3(g), dim3(256), 0, st, a);
+      hipLaunchKernelGGL((k_verify_quad<false, false>), dim3(g), dim3(256), 0, st, a, NoPairArgs{});
     return hipGetLastError();
   }
   if (a.pre)

@@ -261,6 +261,7 @@ struct cpz_ctx {
   // k_pair_setup leaves per pair, their Niels points, and -- once a failing batch reaches its
   // first leaf -- the descriptor table with the resident sets' tables
   DevBuf bp_gh, bp_setup, bp_pts, bp_desc;
+  DevBuf bp_word;  // cpz_verify_each_pairs_device: the index check's word (k_pair_idx_check)
   // partitioned batch check (part.hip): sorted lists / offsets / window sums of one chunk of
   // blocks, every block's partial and fail flag, the sum's scratch, the failing-block list
   DevBuf pt_lists, pt_offs, pt_wsum, pt_part, pt_fail, pt_tmp, pt_blocks, pt_assign;
@@ -2148,7 +2149,7 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
     b->release();
   ctx->rl_flags.release();
   ctx->rl_parts.release();
-  for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc}) b->release();
+  for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc, &ctx->bp_word}) b->release();
 #if defined(CPZ_CLOCK_PROBE)
   for (DevBuf& b : ctx->clk) b.release();
 #endif
@@ -2206,19 +2207,18 @@ int verify_each_pipelined(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], 
   return CPZ_OK;
 }
 
-}  // namespace
-
-int cpz_verify_each_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const void* d_y1,
-                           const void* d_y2, const void* d_r1, const void* d_r2, const void* d_s,
-                           const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
-                           void* d_status_out, void* stream) {
+// cpz_verify_each_device with per-call flags (the one-pair case of cpz_verify_each_pairs_device).
+int verify_each_device_flags(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], const uint8_t h[32], size_t n,
+                             const void* d_y1, const void* d_y2, const void* d_r1, const void* d_r2, const void* d_s,
+                             const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
+                             void* d_status_out, void* stream) {
   if (!ctx || !g || !h) return fail(CPZ_EINVAL, "null context or generators");
   if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
   if (!d_y1 || !d_y2 || !d_r1 || !d_r2 || !d_s || !d_status_out) return fail(CPZ_EINVAL, "null input pointer");
   if (!aligned16(d_y1) || !aligned16(d_y2) || !aligned16(d_r1) || !aligned16(d_r2) || !aligned16(d_s))
     return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
   if (d_ctx_off && !d_ctx_bytes) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
-  CallLock lock(ctx);
+  CallLock lock(ctx, flags);
   CPZ_HIP(hipSetDevice(ctx->device));
   int rc = ensure_generators(ctx, g, h, (int64_t)n > var_base_max(ctx));
   if (rc) return rc;
@@ -2228,6 +2228,16 @@ int cpz_verify_each_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32
                       static_cast<uint8_t*>(d_status_out), st);
   if (rc) return rc;
   return record_last(ctx, st);
+}
+
+}  // namespace
+
+int cpz_verify_each_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const void* d_y1,
+                           const void* d_y2, const void* d_r1, const void* d_r2, const void* d_s,
+                           const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
+                           void* d_status_out, void* stream) {
+  return verify_each_device_flags(ctx, 0, g, h, n, d_y1, d_y2, d_r1, d_r2, d_s, d_ctx_bytes, d_ctx_off, d_ctx_present,
+                                  d_status_out, stream);
 }
 
 int cpz_verify_each(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const uint8_t* y1,
@@ -2293,6 +2303,149 @@ void pair_desc(cpz::PairDesc& d, const GenSet& e) {
   std::memcpy(d.k1, e.chal_k1, sizeof(d.k1));
   std::memcpy(d.k2, e.chal_k2, sizeof(d.k2));
   std::memcpy(d.c32, e.chal_c32, sizeof(d.c32));
+}
+
+// A mixed-pair range on the device: rows, contexts (absolute offsets into cb), indices and
+// statuses of the whole call, the descriptor table with every pair's tables resident, and the
+// challenge buffer (32 bytes per proof of the call).
+struct PairRange {
+  const void* rows[5] = {};  // y1, y2, r1, r2, s
+  const void* cb = nullptr;
+  const uint64_t* co = nullptr;
+  const uint8_t* cp = nullptr;
+  const uint32_t* idx = nullptr;
+  const cpz::PairDesc* desc = nullptr;
+  uint32_t* c = nullptr;
+  uint8_t* status = nullptr;
+};
+
+// Per-proof verification of proofs [lo, hi) of a mixed-pair range on eight lanes per proof, in
+// chunks of at most verify_quad_max(ctx) proofs: k_challenge_pairs, then k_verify_quad_pairs, on
+// the chunk's stream.  The chunks alternate over the verify streams and their slabs as
+// launch_verify_chunks' do and are joined into `st` at the end.  `stage` times the verify launches.
+int launch_quad_pairs_chunks(cpz_ctx* ctx, const PairRange& r, int64_t lo, int64_t hi, int stage, hipStream_t st) {
+  const int64_t per = verify_quad_max(ctx);
+  if (per < 1) return fail(CPZ_EINVAL, "internal: no room for the eight-lane kernel's tables");
+  const size_t slab = verify_slab_bytes(ctx);
+  const int64_t chunks = (hi - lo + per - 1) / per;
+  const int nst = (int)std::min<int64_t>(CPZ_VERIFY_STREAMS, chunks);
+  CPZ_HIP(ctx->scratch.ensure((size_t)CPZ_VERIFY_STREAMS * slab));
+  if (nst > 1) {
+    if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
+    CPZ_HIP(hipEventRecord(ctx->aux_start, st));  // the aux streams start after st's prior work
+    for (int k = 0; k < nst - 1; k++) {
+      if (!ctx->aux_stream[k]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[k], ctx->cus, ctx->device, &ctx->own_queues));
+      if (!ctx->aux_done[k]) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_done[k], hipEventDisableTiming));
+      CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->aux_start, 0));
+    }
+  }
+  for (int64_t c = 0; c < chunks; c++) {
+    const int64_t a = lo + c * per;
+    const int k = (int)(c % nst);  // stream k owns scratch slab k
+    hipStream_t sc = k == 0 ? st : ctx->aux_stream[k - 1];
+    cpz::ChallengeArgs ca{};
+    ca.eq_only = ctx->call_eq ? 1 : 0;
+    ca.n = std::min<int64_t>(hi - a, per);
+    ca.y1 = static_cast<const uint32_t*>(r.rows[0]) + 8 * a;
+    ca.y2 = static_cast<const uint32_t*>(r.rows[1]) + 8 * a;
+    ca.r1 = static_cast<const uint32_t*>(r.rows[2]) + 8 * a;
+    ca.r2 = static_cast<const uint32_t*>(r.rows[3]) + 8 * a;
+    ca.s = static_cast<const uint32_t*>(r.rows[4]) + 8 * a;
+    ca.ctx_bytes = static_cast<const uint8_t*>(r.cb);
+    ca.ctx_off = r.co ? r.co + a : nullptr;  // absolute offsets into ctx_bytes
+    ca.ctx_present = r.cp ? r.cp + a : nullptr;
+    ca.prefix = nullptr;  // per pair: PairDesc
+    ca.c_out = r.c + 8 * a;
+    ca.status_out = r.status + a;
+    cpz::PairArgs pa;
+    pa.desc = r.desc;
+    pa.pair_idx = r.idx + a;
+    cpz::VerifyArgs va{};
+    va.n = ca.n;
+    va.y1 = ca.y1;
+    va.y2 = ca.y2;
+    va.r1 = ca.r1;
+    va.r2 = ca.r2;
+    va.s = ca.s;
+    va.c = ca.c_out;
+    va.status = ca.status_out;
+    va.comb = nullptr;
+    va.eq_only = ca.eq_only;
+    va.quad_max = per;
+    va.scratch = static_cast<char*>(ctx->scratch.p) + (size_t)k * slab;
+    {
+      StageTimer tc(ctx, 0, sc);
+      CPZ_HIP(cpz::launch_challenge_pairs(ca, pa, sc));
+    }
+    StageTimer t(ctx, stage, sc);
+    CPZ_HIP(cpz::launch_verify_quad_pairs(va, pa, sc));
+  }
+  if (nst > 1) return join_verify_streams(ctx, st);
+  return CPZ_OK;
+}
+
+// Whether (g, h) has a resident set, full or light (ensure_generators would build nothing).
+bool pair_resident(const cpz_ctx* ctx, const uint8_t both[64]) {
+  for (int k = 0; k < ctx->gen_cap; k++)
+    if (ctx->gen[k].valid && std::memcmp(ctx->gen[k].gh, both, 64) == 0) return true;
+  for (const GenSet& e : ctx->light)
+    if (e.valid && std::memcmp(e.gh, both, 64) == 0) return true;
+  return false;
+}
+
+// The argument checks of the bulk mixed-pair calls up to the indices, in cpz_verify_each_pairs_ex's
+// order and wording (the indices follow: on the host, or on the device for the device form).
+int pairs_bulk_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const void* pair_idx,
+                           const void* y1, const void* y2, const void* r1, const void* r2, const void* s,
+                           const void* status_out) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
+  if (npairs > CPZ_PAIRS_MAX)
+    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
+                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (n > CPZ_PAIRS_BULK_MAX_PROOFS)
+    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_PAIRS_BULK_MAX_PROOFS (" +
+                                std::to_string(CPZ_PAIRS_BULK_MAX_PROOFS) + ")");
+  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !status_out)
+    return fail(CPZ_EINVAL, "null input pointer");
+  return CPZ_OK;
+}
+
+// Parameters::with_generators (gadgets.rs:77-103) for every pair, on the host, before anything is
+// launched: not the identity, distinct, and -- for a pair without a resident set, whose tables a
+// launch would have to build -- both encodings decode.
+int pairs_bulk_generator_checks(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs) {
+  static const uint8_t zero[32] = {0};
+  for (size_t p = 0; p < npairs; p++) {
+    const uint8_t *g = pairs + 64 * p, *h = g + 32;
+    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
+    if (std::memcmp(g, h, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
+  }
+  CallLock lock(ctx, flags);
+  for (size_t p = 0; p < npairs; p++) {
+    if (pair_resident(ctx, pairs + 64 * p)) continue;
+    uint32_t w[16];
+    std::memcpy(w, pairs + 64 * p, 64);
+    cpz::ge_p3 pt;
+    if (!cpz::ristretto_decode(pt, w) || !cpz::ristretto_decode(pt, w + 8))
+      return fail(CPZ_EGENERATOR,
+                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
+  }
+  return CPZ_OK;
+}
+
+// Every pair of the call resident (light sets at stage 13 unless a full one is cached; no combs)
+// and its descriptor row written to desc[p].
+int pairs_make_resident(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, cpz::PairDesc* desc) {
+  for (size_t p = 0; p < npairs; p++) {
+    int rc = ensure_generators(ctx, pairs + 64 * p, pairs + 64 * p + 32, false, true);
+    if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
+    pair_desc(desc[p], *ctx->gs);
+  }
+  return CPZ_OK;
 }
 
 }  // namespace
@@ -2412,6 +2565,154 @@ int cpz_verify_each_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const 
   return CPZ_OK;
 }
 
+int cpz_verify_each_pairs_bulk(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const uint32_t* pair_idx,
+                               const uint8_t* y1, const uint8_t* y2, const uint8_t* r1, const uint8_t* r2,
+                               const uint8_t* s, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                               const uint8_t* ctx_present, uint8_t* status_out) {
+  return cpz_verify_each_pairs_bulk_ex(ctx, 0, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, ctx_bytes, ctx_off,
+                                       ctx_present, status_out);
+}
+
+int cpz_verify_each_pairs_bulk_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
+                                  const uint32_t* pair_idx, const uint8_t* y1, const uint8_t* y2, const uint8_t* r1,
+                                  const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes,
+                                  const uint64_t* ctx_off, const uint8_t* ctx_present, uint8_t* status_out) {
+  static_assert(CPZ_PAIRS_MAX <= kLightCache, "every pair of a call is resident at once");
+  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, status_out);
+  if (rc) return rc;
+  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  for (size_t i = 0; i < n; i++)
+    if (pair_idx[i] >= npairs)
+      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
+                                  " is not below npairs (" + std::to_string(npairs) + ")");
+  if ((rc = pairs_bulk_generator_checks(ctx, flags, npairs, pairs))) return rc;
+  if (npairs == 1)
+    return cpz_verify_each_ex(ctx, flags, pairs, pairs + 32, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present,
+                              status_out);
+  if (n <= CPZ_PAIRS_MAX_PROOFS)  // the latency kernels' range
+    return cpz_verify_each_pairs_ex(ctx, flags, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, ctx_bytes, ctx_off,
+                                    ctx_present, status_out);
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  // every pair resident at once, then the descriptor table and the indices to the device in one
+  // block with the rows (stage_inputs' extra), as cpz_verify_batch_pairs_ex stages them
+  std::vector<cpz::PairDesc> desc(npairs);
+  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
+  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
+  std::memcpy(extra.data(), desc.data(), npairs * sizeof(cpz::PairDesc));
+  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  if ((rc = order_after_last(ctx, ctx->stream))) return rc;
+  const uint8_t* host[5] = {y1, y2, r1, r2, s};
+  const void* dev[5];
+  const void* dcb;
+  const uint64_t* dco;
+  const uint8_t* dcp;
+  const void* dex = nullptr;
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, false, nullptr, nullptr,
+                    extra.data(), extra.size(), &dex);
+  if (rc) return rc;
+  if (!dex) return fail(CPZ_EHIP, "internal: the pair descriptors were not staged");
+  CPZ_HIP(ctx->st.ensure(n));
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  PairRange r;
+  for (int k = 0; k < 5; k++) r.rows[k] = dev[k];
+  r.cb = dcb;
+  r.co = dco;
+  r.cp = dcp;
+  r.desc = static_cast<const cpz::PairDesc*>(dex);
+  r.idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(dex) + npairs * sizeof(cpz::PairDesc));
+  r.c = static_cast<uint32_t*>(ctx->c.p);
+  r.status = static_cast<uint8_t*>(ctx->st.p);
+  {
+    StageTimer span(ctx, 5, ctx->stream);
+    if ((rc = launch_quad_pairs_chunks(ctx, r, 0, (int64_t)n, 1, ctx->stream))) {
+      (void)hipStreamSynchronize(ctx->stream);
+      return rc;
+    }
+  }
+  const bool pinned = ctx->pin.cap >= kPinMail + pad16(n);
+  uint8_t* dst = pinned ? static_cast<uint8_t*>(ctx->pin.p) + kPinMail : status_out;
+  CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
+  CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (pinned) std::memcpy(status_out, dst, n);
+  return CPZ_OK;
+}
+
+int cpz_verify_each_pairs_device(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
+                                 const uint32_t* d_pair_idx, const void* d_y1, const void* d_y2, const void* d_r1,
+                                 const void* d_r2, const void* d_s, const void* d_ctx_bytes,
+                                 const uint64_t* d_ctx_off, const uint8_t* d_ctx_present, void* d_status_out,
+                                 void* stream) {
+  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, d_pair_idx, d_y1, d_y2, d_r1, d_r2, d_s, d_status_out);
+  if (rc) return rc;
+  if (!aligned16(d_y1) || !aligned16(d_y2) || !aligned16(d_r1) || !aligned16(d_r2) || !aligned16(d_s))
+    return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_pair_idx) & 3) != 0) return fail(CPZ_EINVAL, "d_pair_idx must be 4-byte aligned");
+  if (d_ctx_off && !d_ctx_bytes) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  hipStream_t st = nullptr;
+  {
+    // The indices, on the device: the lowest offending entry in one word, read back here -- no
+    // kernel that follows an index into the descriptor table is enqueued before that.
+    CallLock lock(ctx, flags);
+    CPZ_HIP(hipSetDevice(ctx->device));
+    st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    if ((rc = order_after_last(ctx, st))) return rc;
+    CPZ_HIP(ctx->bp_word.ensure(2 * sizeof(uint32_t)));
+    uint32_t* word = static_cast<uint32_t*>(ctx->bp_word.p);
+    uint32_t first[2] = {cpz::kPairIdxOk, 0};
+    CPZ_HIP(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
+    CPZ_HIP(cpz::launch_pair_idx_check(d_pair_idx, (int64_t)n, (uint32_t)npairs, word, st));
+    CPZ_HIP(hipMemcpyAsync(&first[0], word, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+    if (first[0] != cpz::kPairIdxOk) {
+      CPZ_HIP(hipMemcpyAsync(&first[1], d_pair_idx + first[0], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      CPZ_HIP(hipStreamSynchronize(st));
+      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(first[0]) + "] = " + std::to_string(first[1]) +
+                                  " is not below npairs (" + std::to_string(npairs) + ")");
+    }
+  }
+  if ((rc = pairs_bulk_generator_checks(ctx, flags, npairs, pairs))) return rc;
+  if (npairs == 1) {
+    rc = verify_each_device_flags(ctx, flags, pairs, pairs + 32, n, d_y1, d_y2, d_r1, d_r2, d_s, d_ctx_bytes, d_ctx_off,
+                                  d_ctx_present, d_status_out, stream);
+    if (rc) return rc;
+    CPZ_HIP(hipStreamSynchronize(st));
+    return CPZ_OK;
+  }
+  CallLock lock(ctx, flags);
+  std::vector<cpz::PairDesc> desc(npairs);
+  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
+  CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, desc.data(), npairs * sizeof(cpz::PairDesc), hipMemcpyHostToDevice, st));
+  CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `desc` goes
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  PairRange r;
+  r.rows[0] = d_y1;
+  r.rows[1] = d_y2;
+  r.rows[2] = d_r1;
+  r.rows[3] = d_r2;
+  r.rows[4] = d_s;
+  r.cb = d_ctx_bytes;
+  r.co = d_ctx_off;
+  r.cp = d_ctx_off ? d_ctx_present : nullptr;
+  r.desc = static_cast<const cpz::PairDesc*>(ctx->bp_desc.p);
+  r.idx = d_pair_idx;
+  r.c = static_cast<uint32_t*>(ctx->c.p);
+  r.status = static_cast<uint8_t*>(d_status_out);
+  {
+    StageTimer span(ctx, 5, st);
+    rc = launch_quad_pairs_chunks(ctx, r, 0, (int64_t)n, 1, st);
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  if ((rc = record_last(ctx, st))) return rc;
+  CPZ_HIP(hipStreamSynchronize(st));
+  return CPZ_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2464,8 +2765,9 @@ int pairs_range_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi,
 }
 
 // Per-proof verification of [lo, hi) under every entry's own pair, on the rows already on the
-// device: the mixed-pair latency kernels in pieces of at most CPZ_PAIRS_MAX_PROOFS.  The first
-// leaf makes the call's pairs resident (light sets unless a full one is cached).
+// device: up to CPZ_PAIRS_MAX_PROOFS the mixed-pair latency kernels, above (a range most of whose
+// parts failed) the chunked eight-lane path of cpz_verify_each_pairs_bulk.  The first leaf makes
+// the call's pairs resident (light sets unless a full one is cached).
 int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
   if (!b.d_full) {
     std::vector<cpz::PairDesc> full(b.npairs);
@@ -2480,6 +2782,21 @@ int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t s
     b.d_full = static_cast<const cpz::PairDesc*>(ctx->bp_desc.p);
   }
   ctx->fb_stats[4] += (uint64_t)(hi - lo);
+  // a dense range: the chunked eight-lane path (CPZ_PAIRS_LEAF_QUAD=0 in the environment, read at
+  // every call, restores the serial latency launches: for measurement, tools/pairs_bulk_ab.py)
+  const char* leaf_quad = std::getenv("CPZ_PAIRS_LEAF_QUAD");
+  if (hi - lo > (int64_t)CPZ_PAIRS_MAX_PROOFS && !(leaf_quad && leaf_quad[0] == '0')) {
+    PairRange r;
+    for (int k = 0; k < 5; k++) r.rows[k] = b.rows[k];
+    r.cb = b.cb;
+    r.co = b.co;
+    r.cp = b.cp;
+    r.idx = b.d_idx;
+    r.desc = b.d_full;
+    r.c = static_cast<uint32_t*>(ctx->c.p);  // n x 32, the batch's challenges: rewritten with the same values
+    r.status = b.d_status;
+    return launch_quad_pairs_chunks(ctx, r, lo, hi, 4, st);
+  }
   for (int64_t a = lo; a < hi; a += CPZ_PAIRS_MAX_PROOFS) {
     const int64_t m = std::min<int64_t>(hi - a, CPZ_PAIRS_MAX_PROOFS);
     cpz::ChallengeArgs ca{};

@@ -124,7 +124,8 @@ int cpz_verify_each_ex(cpz_ctx *ctx, uint32_t flags, const uint8_t g[32], const 
  * n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_PAIRS_MAX, n > CPZ_PAIRS_MAX_PROOFS, a null
  * pointer or a pair_idx[i] >= npairs -> CPZ_EINVAL; a pair that is the identity, has g == h
  * or does not decode -> CPZ_EGENERATOR.  Host buffers only: the indices are checked on the
- * host. */
+ * host.  For more than CPZ_PAIRS_MAX_PROOFS entries, or for rows already on the device, use
+ * cpz_verify_each_pairs_bulk / cpz_verify_each_pairs_device below. */
 #define CPZ_PAIRS_MAX 64
 #define CPZ_PAIRS_MAX_PROOFS 2048
 int cpz_verify_each_pairs(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
@@ -138,7 +139,49 @@ int cpz_verify_each_pairs_ex(cpz_ctx *ctx, uint32_t flags, size_t npairs, const 
                              const uint8_t *ctx_bytes, const uint64_t *ctx_off,
                              const uint8_t *ctx_present, uint8_t *status_out);
 
-/* Same with device-resident, 16-byte aligned inputs/outputs, enqueued on `stream`
+/* The mixed-pair per-proof call without the latency kernels' bound: up to
+ * CPZ_PAIRS_BULK_MAX_PROOFS entries, from host buffers or from device-resident rows.  Every
+ * argument means what it means for cpz_verify_each_pairs, and status_out[i] is what
+ * cpz_verify_each_ex reports for entry i under pairs[pair_idx[i]] -- every status, with
+ * CPZ_CALL_EQUATIONS_ONLY, the context's commitment-check mode and every context shape; rows of
+ * `pairs` may repeat and may be the default pair.
+ *   npairs == 1 is cpz_verify_each_ex (the device form: cpz_verify_each_device) under that pair.
+ *   The host form with n <= CPZ_PAIRS_MAX_PROOFS is cpz_verify_each_pairs_ex.
+ *   Otherwise every pair is made resident at once (light sets, stage 13; no combs), and the
+ *   entries are verified in chunks of at most 16384 proofs (14080 on a 110-CU part: the table
+ *   slab's bound), eight lanes per proof, every proof from its own pair's 128-entry tables; the
+ *   chunks alternate over the context's verify streams and are joined at the end.
+ * Both forms return synchronised.  The device form takes 16-byte aligned device rows and n
+ * device-resident indices (`pairs` stays a host array of 64-byte rows), on `stream` (a
+ * hipStream_t, or NULL for the context's own stream).  It first scans the indices on the device
+ * and synchronises `stream` to read the result: no kernel that follows an index is enqueued
+ * before that, and an offending index is CPZ_EINVAL naming the lowest such entry with
+ * d_status_out untouched.  It then enqueues the chunks and synchronises `stream` again before it
+ * returns.  Any later call on the same context, on any stream, is ordered after this call's
+ * kernels (they read the context's cached tables and work buffers).
+ * Checked before anything is launched (the device form: before anything but the index scan) or
+ * written, in cpz_verify_each_pairs' order and wording, cpz_last_error naming the pair or the
+ * entry: n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_PAIRS_MAX,
+ * n > CPZ_PAIRS_BULK_MAX_PROOFS, a null pointer or a pair_idx[i] >= npairs -> CPZ_EINVAL; a pair
+ * that is the identity, has g == h or does not decode -> CPZ_EGENERATOR. */
+#define CPZ_PAIRS_BULK_MAX_PROOFS 1048576 /* 1 << 20, as CPZ_BATCH_PAIRS_MAX_PROOFS */
+int cpz_verify_each_pairs_bulk(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
+                               const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                               const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                               const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                               const uint8_t *ctx_present, uint8_t *status_out);
+int cpz_verify_each_pairs_bulk_ex(cpz_ctx *ctx, uint32_t flags, size_t npairs, const uint8_t *pairs, size_t n,
+                                  const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                                  const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                                  const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                                  const uint8_t *ctx_present, uint8_t *status_out);
+int cpz_verify_each_pairs_device(cpz_ctx *ctx, uint32_t flags, size_t npairs, const uint8_t *pairs, size_t n,
+                                 const uint32_t *d_pair_idx, const void *d_y1, const void *d_y2,
+                                 const void *d_r1, const void *d_r2, const void *d_s,
+                                 const void *d_ctx_bytes, const uint64_t *d_ctx_off,
+                                 const uint8_t *d_ctx_present, void *d_status_out, void *stream);
+
+/* cpz_verify_each with device-resident, 16-byte aligned inputs/outputs, enqueued on `stream`
  * (a hipStream_t, or NULL for the context's own stream, which is a blocking stream and so
  * is ordered with the legacy default stream).  Does not synchronise.  Any later call on the
  * same context, on any stream, is ordered after this call's kernels (they read the context's
@@ -256,10 +299,12 @@ int cpz_verify_batch_device(cpz_ctx *ctx, const uint8_t g[32], const uint8_t h[3
  * the per-pair sums of a_i s_i and b_i s_i as scalars, so a batch that passes builds no table
  * and no comb, whatever its pairs: only a failing batch with status_out makes its pairs resident
  * (light sets, stage 13), when its bisection reaches the first range of at most
- * CPZ_PAIRS_MAX_PROOFS entries, which the mixed-pair per-proof kernels verify.  With every pair's
- * tables already resident and n <= CPZ_PAIRS_MAX_PROOFS, cpz_verify_each_pairs is the faster call
- * (one launch); this one is for pairs the context has not seen, or too many to keep, and for
- * larger n.
+ * CPZ_PAIRS_MAX_PROOFS entries, which the mixed-pair latency kernels verify, or a range most of
+ * whose eight parts fail, which goes through cpz_verify_each_pairs_bulk's chunked eight-lane
+ * path.  With every pair's tables already resident and n <= CPZ_PAIRS_MAX_PROOFS,
+ * cpz_verify_each_pairs is the faster call (one launch); a caller that wants exact statuses of a
+ * larger set whatever its validity calls cpz_verify_each_pairs_bulk; this one is for sets
+ * expected to pass, and for pairs the context has not seen or too many to keep.
  *   partial_out, batch_ok   as for cpz_verify_batch (both required); shards with global
  *                first_index values combine (cpz_combine_partials) to the unsharded P.
  *   status_out   optional (n).  Entries with a non-zero decode-level status carry zero weight and

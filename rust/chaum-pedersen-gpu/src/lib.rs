@@ -249,6 +249,33 @@ impl Gpu {
         Ok(st)
     }
 
+    /// `verify_each_pairs` without its entry bound (`cpz_verify_each_pairs_bulk_ex`): at most
+    /// `CPZ_PAIRS_MAX` pairs and `CPZ_PAIRS_BULK_MAX_PROOFS` entries.  Up to `CPZ_PAIRS_MAX_PROOFS`
+    /// entries it is `verify_each_pairs`; above, the entries are verified in chunks of at most 16384
+    /// on eight lanes per proof, each from its own pair's tables.  The same statuses either way.
+    pub fn verify_each_pairs_bulk(&self, flags: CallFlags, pairs: &[(Bytes32, Bytes32)], pair_idx: &[u32],
+                                  entries: &[Entry<'_>]) -> Result<Vec<u8>, GpuError> {
+        if pair_idx.len() != entries.len() {
+            return Err(GpuError { code: sys::CPZ_EINVAL, message: "pair_idx must hold one index per entry".into() });
+        }
+        let mut gh = Vec::with_capacity(64 * pairs.len());
+        for (g, h) in pairs {
+            gh.extend_from_slice(g);
+            gh.extend_from_slice(h);
+        }
+        let soa = Soa::new(entries);
+        let (cb, co, cp) = soa.ctx_ptrs();
+        let mut st = vec![0u8; entries.len()];
+        let r = &soa.rows;
+        // SAFETY: as verify_each_pairs.
+        check(unsafe {
+            sys::cpz_verify_each_pairs_bulk_ex(self.ctx, flags, pairs.len(), gh.as_ptr(), entries.len(),
+                                               pair_idx.as_ptr(), r[0].as_ptr(), r[1].as_ptr(), r[2].as_ptr(),
+                                               r[3].as_ptr(), r[4].as_ptr(), cb, co, cp, st.as_mut_ptr())
+        })?;
+        Ok(st)
+    }
+
     /// The batch check over entries that carry their own generators, in one MSM
     /// (`cpz_verify_batch_pairs_ex`): entry i stands under `pairs[pair_idx[i]]`, at most
     /// `CPZ_PAIRS_MAX` pairs and `CPZ_BATCH_PAIRS_MAX_PROOFS` entries.  Returns (partial encoding,
