@@ -285,6 +285,20 @@ def _pair_indices(pair_idx, n: int, npairs: int) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
+def _pair_index_tensor(pair_idx, n: int) -> None:
+    """pair_idx of the device forms: a contiguous int32 or uint32 device tensor of n elements (its
+    values are checked by the library, on the device)."""
+    dtype = str(getattr(pair_idx, "dtype", None))
+    if not hasattr(pair_idx, "data_ptr") or dtype not in ("torch.int32", "torch.uint32"):
+        raise InvalidParams("pair_idx must be an int32 or uint32 device tensor, not %s (%s)"
+                            % (type(pair_idx).__name__, dtype))
+    if pair_idx.dim() != 1 or int(pair_idx.numel()) != n or not pair_idx.is_contiguous():
+        raise InvalidParams("pair_idx must hold one index per proof: shape %s for %d proofs"
+                            % (tuple(pair_idx.shape), n))
+    if not pair_idx.is_cuda:
+        raise InvalidParams("pair_idx must be a device tensor (it is on %s)" % pair_idx.device)
+
+
 def _ptr(a) -> Optional[int]:
     return None if a is None else a.ctypes.data
 
@@ -463,6 +477,27 @@ class Gpu:
                                           _ptr(present), *[_ptr(outs[q]) for q in ("y1", "y2", "r1", "r2", "s")]))
         return outs
 
+    def prove_pairs(self, pairs: Sequence[Parameters], pair_idx, x, k, contexts=None):
+        """prove with a pair per proof, in one call (cpz_prove_pairs): entry i is proven under
+        pairs[pair_idx[i]] and its rows are byte for byte what prove writes for it under that pair.
+        At most PAIRS_MAX pairs and PROVE_PAIRS_MAX_PROOFS proofs; every point comes from its
+        pair's 128-entry tables, and no comb is built for any pair.  x, k, contexts as prove
+        takes them; pair_idx: n integers in [0, len(pairs)), checked here before the library is
+        called.  Returns the dict of (n, 32) arrays y1, y2, r1, r2, s."""
+        n = len(x)
+        npairs = len(pairs)
+        idx = _pair_indices(pair_idx, n, npairs)
+        xs = x if isinstance(x, np.ndarray) else np.frombuffer(b"".join(_scalar_bytes(v) for v in x), np.uint8)
+        ks = k if isinstance(k, np.ndarray) else np.frombuffer(b"".join(_scalar_bytes(v) for v in k), np.uint8)
+        xs, ks = _rows(xs, n, "x"), _rows(ks, n, "k")
+        gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+        outs = {q: np.empty((n, 32), dtype=np.uint8) for q in ("y1", "y2", "r1", "r2", "s")}
+        blob, off, present = _ctx_arrays(contexts, n)
+        _native.check(self._lib.cpz_prove_pairs(
+            self._h, npairs, _ptr(gh), n, _ptr(idx), _ptr(xs), _ptr(ks), _ptr(blob), _ptr(off), _ptr(present),
+            *[_ptr(outs[q]) for q in ("y1", "y2", "r1", "r2", "s")]))
+        return outs
+
     def decode_points(self, points):
         """Bulk element_from_bytes + element_to_bytes (cpz_decode_points): (ok uint8[n],
         re-encodings uint8[n, 32], zero where a point does not decode)."""
@@ -603,15 +638,7 @@ class Gpu:
         [0, len(pairs)) raises CpzError with CPZ_EINVAL and leaves status_out untouched).  Returns
         with `stream` synchronised and status_out filled."""
         n = int(y1.shape[0])
-        dtype = str(getattr(pair_idx, "dtype", None))
-        if not hasattr(pair_idx, "data_ptr") or dtype not in ("torch.int32", "torch.uint32"):
-            raise InvalidParams("pair_idx must be an int32 or uint32 device tensor, not %s (%s)"
-                                % (type(pair_idx).__name__, dtype))
-        if pair_idx.dim() != 1 or int(pair_idx.numel()) != n or not pair_idx.is_contiguous():
-            raise InvalidParams("pair_idx must hold one index per proof: shape %s for %d proofs"
-                                % (tuple(pair_idx.shape), n))
-        if not pair_idx.is_cuda:
-            raise InvalidParams("pair_idx must be a device tensor (it is on %s)" % pair_idx.device)
+        _pair_index_tensor(pair_idx, n)
         npairs = len(pairs)
         gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
         dp = lambda t: None if t is None else t.data_ptr()
@@ -636,6 +663,22 @@ class Gpu:
             self._h, params.g, params.h, int(x.shape[0]), x.data_ptr(), k.data_ptr(), dp(ctx_bytes), dp(ctx_off),
             dp(ctx_present), y1.data_ptr(), y2.data_ptr(), r1.data_ptr(), r2.data_ptr(), s.data_ptr(),
             _torch_stream(stream)))
+
+    def prove_pairs_device(self, pairs: Sequence[Parameters], pair_idx, x, k, y1, y2, r1, r2, s,
+                           stream: Optional[int] = None, ctx_bytes=None, ctx_off=None, ctx_present=None) -> None:
+        """prove_pairs on device tensors (cpz_prove_pairs_device): witnesses x, nonces k and the
+        five output rows uint8 (n, 32), 16-B aligned; pair_idx an int32 or uint32 device tensor of n
+        elements, whose values the library checks on the device before any kernel follows them (an
+        index outside [0, len(pairs)) raises CpzError with CPZ_EINVAL and leaves the outputs
+        untouched).  Returns with `stream` synchronised and the outputs filled."""
+        n = int(x.shape[0])
+        _pair_index_tensor(pair_idx, n)
+        npairs = len(pairs)
+        gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+        dp = lambda t: None if t is None else t.data_ptr()
+        _native.check(self._lib.cpz_prove_pairs_device(
+            self._h, npairs, _ptr(gh), n, dp(pair_idx), dp(x), dp(k), dp(ctx_bytes), dp(ctx_off), dp(ctx_present),
+            dp(y1), dp(y2), dp(r1), dp(r2), dp(s), _torch_stream(stream)))
 
     def prove_synthetic_device(self, n: int, seed_x: bytes, seed_k: bytes, y1, y2, r1, r2, s, first_index: int = 0,
                                params: Optional[Parameters] = None, stream: Optional[int] = None,

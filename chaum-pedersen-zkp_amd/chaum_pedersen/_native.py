@@ -37,11 +37,13 @@ EXPORTED = (
     "cpz_verify_each_ex", "cpz_verify_batch_ex", "cpz_verify_response_ex",
     "cpz_verify_each_pairs", "cpz_verify_each_pairs_ex", "cpz_verify_batch_pairs", "cpz_verify_batch_pairs_ex",
     "cpz_verify_each_pairs_bulk", "cpz_verify_each_pairs_bulk_ex", "cpz_verify_each_pairs_device",
+    "cpz_prove_pairs", "cpz_prove_pairs_device",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
 BATCH_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_BATCH_PAIRS_MAX_PROOFS: proofs per cpz_verify_batch_pairs call
 PAIRS_BULK_MAX_PROOFS = 1 << 20    # CPZ_PAIRS_BULK_MAX_PROOFS: proofs per cpz_verify_each_pairs_bulk / _device call
+PROVE_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_PROVE_PAIRS_MAX_PROOFS: proofs per cpz_prove_pairs / _device call
 CALL_EQUATIONS_ONLY = 1   # CPZ_CALL_EQUATIONS_ONLY: commitment checks off for one call
 NUM_STAGES = 16
 FALLBACK_STATS = 8
@@ -140,6 +142,11 @@ def _declare(lib):
     lib.cpz_prove.argtypes = [_p, _p, _p, ctypes.c_size_t, _p, _p, _p, _p, _p] + [_p] * 5
     lib.cpz_prove_device.restype = ctypes.c_int
     lib.cpz_prove_device.argtypes = [_p, _p, _p, ctypes.c_size_t, _p, _p, _p, _p, _p] + [_p] * 5 + [_p]
+    lib.cpz_prove_pairs.restype = ctypes.c_int
+    lib.cpz_prove_pairs.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p, _p, _p, _p, _p] + [_p] * 5)
+    lib.cpz_prove_pairs_device.restype = ctypes.c_int
+    lib.cpz_prove_pairs_device.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p, _p, _p, _p, _p] +
+                                           [_p] * 5 + [_p])
     lib.cpz_decode_points.restype = ctypes.c_int
     lib.cpz_decode_points.argtypes = [_p, ctypes.c_size_t, _p, _p, _p]
     lib.cpz_abi_version.restype = ctypes.c_int

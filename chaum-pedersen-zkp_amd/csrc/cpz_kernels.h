@@ -14,16 +14,14 @@ constexpr uint8_t kStatusBadScalar = 3;
 constexpr uint8_t kStatusIdentity = 4;
 constexpr uint8_t kStatusZeroS = 5;
 
-constexpr int kNielsEntries = kTableB;   // radix-256 signed digits: |d| <= 128
 // Niels table bases per generator: 2^(32 m) B for the level order m = 0, 4, 2, 6, 1, 3, 5, 7
 // (B, 2^128 B: the eight-lane kernels' two 128-bit parts; all eight: k_verify_wide's 32-bit
-// parts), tables [level][generator]
+// parts and the mixed-pair prover's), tables [level][generator] of kNielsEntries entries
+// (scalarmul.h, with kNielsLevelOfPart: the level holding 2^(32 q) B)
 constexpr int kNielsLevels = 8;
 __host__ __device__ constexpr int niels_level_doublings(int level) {
   return level == 0 ? 0 : (level == 1 ? 128 : (level == 2 ? 64 : (level == 3 ? 192 : 32 * (2 * (level - 4) + 1))));
 }
-// the level holding 2^(32 q) B: k_verify_wide's part q of s'
-constexpr int kNielsLevelOfPart[8] = {0, 4, 2, 5, 1, 6, 3, 7};
 constexpr bool niels_parts_consistent() {
   for (int q = 0; q < 8; q++)
     if (niels_level_doublings(kNielsLevelOfPart[q]) != 32 * q) return false;
@@ -214,7 +212,7 @@ struct ProveArgs {
   uint32_t seed_k[8];
   const uint32_t* x_in;          // caller witnesses / nonces (n x 8 words, taken mod l), or null:
   const uint32_t* k_in;          // derived from seed_x / seed_k (synthetic inputs)
-  const ge_niels* comb;          // fixed-base combs of g then h
+  const ge_niels* comb;          // fixed-base combs of g then h (k_prove_points_pairs: unused)
   uint32_t* y1;
   uint32_t* y2;
   uint32_t* r1;
@@ -265,6 +263,9 @@ constexpr uint32_t kPairIdxOk = 0xffffffffu;
 hipError_t launch_pair_idx_check(const uint32_t* idx, int64_t n, uint32_t npairs, uint32_t* first, hipStream_t st);
 int verify_each_blocks_per_cu();  // resident k_verify_each blocks per CU (occupancy API)
 hipError_t launch_prove_points(const ProveArgs& a, hipStream_t st);
+// k_prove_points with a pair per proof (PairArgs): every proof's points from its own pair's Niels
+// tables (PairDesc::tab, all eight levels); a.comb is unused.
+hipError_t launch_prove_points_pairs(const ProveArgs& a, const PairArgs& pa, hipStream_t st);
 hipError_t launch_prove_response(const ProveArgs& a, hipStream_t st);
 // Bulk decode (+ re-encode when out != null) of n encodings.
 hipError_t launch_decode_encode(int64_t n, const uint32_t* pts, uint8_t* ok, uint32_t* out, hipStream_t st);

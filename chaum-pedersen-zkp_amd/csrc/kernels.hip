@@ -22,6 +22,7 @@
 //   k_parse_proofs       bulk Proof::from_bytes (gadgets.rs:364-489) into SoA rows + codes
 //   k_prove_points /     synthetic-input generator: Prover::prove_with_transcript
 //   k_prove_response     (prover/mod.rs:86-131) with ChaCha20-derived witnesses/nonces
+//   k_prove_points_pairs the same points with a (g, h) pair per proof, from the pair's Niels tables
 //
 // Status codes (uint8 per proof): 0 valid, 1 equation failed, 2 undecodable point,
 // 3 non-canonical s, 4 identity commitment, 5 zero s.
@@ -488,6 +489,37 @@ __global__ void __launch_bounds__(kVerifyBlock, 2) k_prove_points(ProveArgs a) {
   store_words8(a.r1, i, w);
   ristretto_encode(w, comb_mul(comb_h, d));
   store_words8(a.r2, i, w);
+}
+
+// Mixed-pair prover (cpz_prove_pairs): proof i's points from the Niels tables of its own pair,
+// pa.desc[pa.pair_idx[i]].tab -- multiples 1..128 of 2^(32 m) g and 2^(32 m) h -- by
+// pair_table_mul (scalarmul.h): [x] g and [x] h in one walk, [k] g and [k] h in a second, 24
+// doublings and at most 32 additions per product.  No comb is read (a.comb is unused), so no
+// pair needs one built.  The 64 lanes of a wave gather different 128-byte entries, from up to 64
+// pairs' tables (245 KB each, 15 MB for 64 pairs: more than an XCD's L2 holds).  Two waves per
+// SIMD as k_prove_points: the two running sums and the two entries of a step are ~140 live VGPRs.
+__global__ void __launch_bounds__(kVerifyBlock, 2) k_prove_points_pairs(ProveArgs a, PairArgs pa) {
+  const int64_t i = (int64_t)blockIdx.x * kVerifyBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const uint64_t idx = a.first_index + (uint64_t)i;
+  const ge_niels* tab = pa.desc[pa.pair_idx[i]].tab;
+  // pass 0: x -> y1, y2; pass 1: k -> r1, r2 (one copy of the walk and of the encoding)
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {
+    uint32_t d[8], w[8];
+    {
+      const sc v = prove_scalar(pass ? a.k_in : a.x_in, pass ? a.seed_k : a.seed_x, idx, i);
+      sc_recode_radix256(d, v.w);
+    }
+    ge_p3 G, H;
+    pair_table_mul(G, H, tab, d);
+#pragma unroll 1
+    for (int e = 0; e < 2; e++) {
+      ristretto_encode(w, G);
+      G = H;
+      store_words8(e ? (pass ? a.r2 : a.y2) : (pass ? a.r1 : a.y1), i, w);
+    }
+  }
 }
 
 __global__ void k_prove_response(ProveArgs a) {
@@ -1150,6 +1182,14 @@ hipError_t launch_prove_points(const ProveArgs& a, hipStream_t st) {
   if (a.n <= 0) return hipSuccess;
   const int64_t blocks = (a.n + kVerifyBlock - 1) / kVerifyBlock;
   hipLaunchKernelGGL(k_prove_points, dim3((unsigned)blocks), dim3(kVerifyBlock), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_prove_points_pairs(const ProveArgs& a, const PairArgs& pa, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (!pa.desc || !pa.pair_idx) return hipErrorInvalidValue;
+  const int64_t blocks = (a.n + kVerifyBlock - 1) / kVerifyBlock;
+  hipLaunchKernelGGL(k_prove_points_pairs, dim3((unsigned)blocks), dim3(kVerifyBlock), 0, st, a, pa);
   return hipGetLastError();
 }
 

@@ -262,6 +262,7 @@ struct cpz_ctx {
   // first leaf -- the descriptor table with the resident sets' tables
   DevBuf bp_gh, bp_setup, bp_pts, bp_desc;
   DevBuf bp_word;  // cpz_verify_each_pairs_device: the index check's word (k_pair_idx_check)
+  DevBuf pp_idx;   // cpz_prove_pairs: the call's pair indices (its descriptors go to bp_desc)
   // partitioned batch check (part.hip): sorted lists / offsets / window sums of one chunk of
   // blocks, every block's partial and fail flag, the sum's scratch, the failing-block list
   DevBuf pt_lists, pt_offs, pt_wsum, pt_part, pt_fail, pt_tmp, pt_blocks, pt_assign;
@@ -2149,7 +2150,7 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
     b->release();
   ctx->rl_flags.release();
   ctx->rl_parts.release();
-  for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc, &ctx->bp_word}) b->release();
+  for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc, &ctx->bp_word, &ctx->pp_idx}) b->release();
 #if defined(CPZ_CLOCK_PROBE)
   for (DevBuf& b : ctx->clk) b.release();
 #endif
@@ -3258,6 +3259,74 @@ int verify_response_impl(cpz_ctx* ctx, size_t n, const void* y1, const void* y2,
   return launch_verify_chunks(ctx, va, 1, st, nullptr, true);
 }
 
+// ---- mixed-pair prover (cpz_prove_pairs) -----------------------------------------------------
+// The argument checks of both forms up to the indices, in cpz_verify_each_pairs_ex's order (the
+// indices follow: on the host, or on the device for the device form).
+int prove_pairs_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const void* pair_idx,
+                            const void* const rows[7]) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "empty input");
+  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
+  if (npairs > CPZ_PAIRS_MAX)
+    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
+                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (n > CPZ_PROVE_PAIRS_MAX_PROOFS)
+    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_PROVE_PAIRS_MAX_PROOFS (" +
+                                std::to_string(CPZ_PROVE_PAIRS_MAX_PROOFS) + ")");
+  if (!pairs || !pair_idx) return fail(CPZ_EINVAL, "null input pointer");
+  for (int q = 0; q < 7; q++)
+    if (!rows[q]) return fail(CPZ_EINVAL, "null input or output pointer");
+  return CPZ_OK;
+}
+
+// prove_impl with a pair per proof: proof i under d_desc[d_idx[i]] (every index in range, every
+// pair's tables resident).  The points come from the pairs' Niels tables (k_prove_points_pairs:
+// no comb, no table slab, so one launch for any n), the challenges from k_challenge_pairs with
+// each pair's transcript prefix, the responses from k_prove_response.
+int prove_pairs_impl(cpz_ctx* ctx, size_t n, const cpz::PairDesc* d_desc, const uint32_t* d_idx, const void* d_x,
+                     const void* d_k, const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
+                     void* d_y1, void* d_y2, void* d_r1, void* d_r2, void* d_s, hipStream_t st) {
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  cpz::ProveArgs pa;
+  pa.n = (int64_t)n;
+  pa.first_index = 0;
+  std::memset(pa.seed_x, 0, 32);
+  std::memset(pa.seed_k, 0, 32);
+  pa.x_in = static_cast<const uint32_t*>(d_x);
+  pa.k_in = static_cast<const uint32_t*>(d_k);
+  pa.comb = nullptr;  // unused: the pairs' Niels tables
+  pa.y1 = static_cast<uint32_t*>(d_y1);
+  pa.y2 = static_cast<uint32_t*>(d_y2);
+  pa.r1 = static_cast<uint32_t*>(d_r1);
+  pa.r2 = static_cast<uint32_t*>(d_r2);
+  pa.c = static_cast<const uint32_t*>(ctx->c.p);
+  pa.s_out = static_cast<uint32_t*>(d_s);
+  cpz::PairArgs pr;
+  pr.desc = d_desc;
+  pr.pair_idx = d_idx;
+  {
+    StageTimer t(ctx, 6, st);
+    CPZ_HIP(cpz::launch_prove_points_pairs(pa, pr, st));
+  }
+  cpz::ChallengeArgs ca{};
+  ca.n = (int64_t)n;
+  ca.y1 = pa.y1;
+  ca.y2 = pa.y2;
+  ca.r1 = pa.r1;
+  ca.r2 = pa.r2;
+  ca.s = nullptr;  // no response yet: no status either
+  ca.ctx_bytes = static_cast<const uint8_t*>(d_ctx_bytes);
+  ca.ctx_off = d_ctx_off;
+  ca.ctx_present = d_ctx_off ? d_ctx_present : nullptr;
+  ca.prefix = nullptr;  // per pair: PairDesc
+  ca.c_out = static_cast<uint32_t*>(ctx->c.p);
+  ca.status_out = nullptr;
+  StageTimer t(ctx, 6, st);
+  CPZ_HIP(cpz::launch_challenge_pairs(ca, pr, st));
+  CPZ_HIP(cpz::launch_prove_response(pa, st));
+  return CPZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3292,6 +3361,107 @@ int cpz_prove(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, 
   if (!x || !k || !y1 || !y2 || !r1 || !r2 || !s) return fail(CPZ_EINVAL, "null input or output pointer");
   if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
   return prove_host(ctx, g, h, n, 0, nullptr, nullptr, x, k, ctx_bytes, ctx_off, ctx_present, y1, y2, r1, r2, s);
+}
+
+int cpz_prove_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const uint32_t* pair_idx,
+                    const uint8_t* x, const uint8_t* k, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                    const uint8_t* ctx_present, uint8_t* y1, uint8_t* y2, uint8_t* r1, uint8_t* r2, uint8_t* s) {
+  static_assert(CPZ_PAIRS_MAX <= kLightCache, "every pair of a call is resident at once");
+  const void* rows[7] = {x, k, y1, y2, r1, r2, s};
+  int rc = prove_pairs_head_checks(ctx, npairs, pairs, n, pair_idx, rows);
+  if (rc) return rc;
+  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  for (size_t i = 0; i < n; i++)
+    if (pair_idx[i] >= npairs)
+      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
+                                  " is not below npairs (" + std::to_string(npairs) + ")");
+  if ((rc = pairs_bulk_generator_checks(ctx, 0, npairs, pairs))) return rc;
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  // every pair resident at once (light sets unless a full one is cached: no comb for any npairs)
+  std::vector<cpz::PairDesc> desc(npairs);
+  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
+  if ((rc = order_after_last(ctx, ctx->stream))) return rc;
+  const void* dcb = nullptr;
+  const uint64_t* dco = nullptr;
+  const uint8_t* dcp = nullptr;
+  const void* unused[5];
+  const uint8_t* none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  rc = stage_inputs(ctx, n, none, 0, ctx_bytes, ctx_off, ctx_present, unused, &dcb, &dco, &dcp);
+  if (rc) return rc;
+  for (int q = 0; q < 7; q++) CPZ_HIP(ctx->in[q].ensure(n * 32));
+  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
+  CPZ_HIP(ctx->pp_idx.ensure(n * sizeof(uint32_t)));
+  CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, desc.data(), npairs * sizeof(cpz::PairDesc), hipMemcpyHostToDevice,
+                         ctx->stream));
+  CPZ_HIP(hipMemcpyAsync(ctx->pp_idx.p, pair_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  CPZ_HIP(hipMemcpyAsync(ctx->in[5].p, x, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  CPZ_HIP(hipMemcpyAsync(ctx->in[6].p, k, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  CPZ_HIP(hipStreamSynchronize(ctx->stream));  // pageable sources: read before `desc` goes
+  rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p),
+                        static_cast<const uint32_t*>(ctx->pp_idx.p), ctx->in[5].p, ctx->in[6].p, dcb, dco, dcp,
+                        ctx->in[0].p, ctx->in[1].p, ctx->in[2].p, ctx->in[3].p, ctx->in[4].p, ctx->stream);
+  if (rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  uint8_t* outs[5] = {y1, y2, r1, r2, s};
+  for (int q = 0; q < 5; q++)
+    CPZ_HIP(hipMemcpyAsync(outs[q], ctx->in[q].p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  return CPZ_OK;
+}
+
+int cpz_prove_pairs_device(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const uint32_t* d_pair_idx,
+                           const void* d_x, const void* d_k, const void* d_ctx_bytes, const uint64_t* d_ctx_off,
+                           const uint8_t* d_ctx_present, void* d_y1, void* d_y2, void* d_r1, void* d_r2, void* d_s,
+                           void* stream) {
+  const void* rows[7] = {d_x, d_k, d_y1, d_y2, d_r1, d_r2, d_s};
+  int rc = prove_pairs_head_checks(ctx, npairs, pairs, n, d_pair_idx, rows);
+  if (rc) return rc;
+  if (!rows_aligned(rows, 7)) return fail(CPZ_EINVAL, "device rows must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_pair_idx) & 3) != 0) return fail(CPZ_EINVAL, "d_pair_idx must be 4-byte aligned");
+  if (d_ctx_off && !d_ctx_bytes) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  hipStream_t st = nullptr;
+  {
+    // The indices, on the device, as cpz_verify_each_pairs_device checks them: the lowest
+    // offending entry in one word, read back here before any kernel that follows an index into
+    // the descriptor table is enqueued, and before any output is written.
+    CallLock lock(ctx);
+    CPZ_HIP(hipSetDevice(ctx->device));
+    st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    if ((rc = order_after_last(ctx, st))) return rc;
+    CPZ_HIP(ctx->bp_word.ensure(2 * sizeof(uint32_t)));
+    uint32_t* word = static_cast<uint32_t*>(ctx->bp_word.p);
+    uint32_t first[2] = {cpz::kPairIdxOk, 0};
+    CPZ_HIP(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
+    CPZ_HIP(cpz::launch_pair_idx_check(d_pair_idx, (int64_t)n, (uint32_t)npairs, word, st));
+    CPZ_HIP(hipMemcpyAsync(&first[0], word, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+    if (first[0] != cpz::kPairIdxOk) {
+      CPZ_HIP(hipMemcpyAsync(&first[1], d_pair_idx + first[0], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      CPZ_HIP(hipStreamSynchronize(st));
+      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(first[0]) + "] = " + std::to_string(first[1]) +
+                                  " is not below npairs (" + std::to_string(npairs) + ")");
+    }
+  }
+  if ((rc = pairs_bulk_generator_checks(ctx, 0, npairs, pairs))) return rc;
+  CallLock lock(ctx);
+  std::vector<cpz::PairDesc> desc(npairs);
+  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
+  CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, desc.data(), npairs * sizeof(cpz::PairDesc), hipMemcpyHostToDevice, st));
+  CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `desc` goes
+  rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p), d_pair_idx, d_x, d_k, d_ctx_bytes,
+                        d_ctx_off, d_ctx_present, d_y1, d_y2, d_r1, d_r2, d_s, st);
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  if ((rc = record_last(ctx, st))) return rc;
+  CPZ_HIP(hipStreamSynchronize(st));
+  return CPZ_OK;
 }
 
 int cpz_prove_synthetic_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n,

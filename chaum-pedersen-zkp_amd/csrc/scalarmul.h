@@ -413,6 +413,73 @@ CPZ_HD ge_p3 fixed_base_mul(const ge_niels* tab_b, const uint32_t sdig_in[8]) {
   return p1p1_to_p3(cur);
 }
 
+// One (g, h) pair's Niels tables (GenSet::tab; k_niels_bases / k_build_niels): multiples 1..128 of
+// 2^(32 m) g and 2^(32 m) h, m = 0..7, as [level][generator][128 entries] with the levels in the
+// order m = 0, 4, 2, 6, 1, 3, 5, 7 (cpz_kernels.h, niels_level_doublings).
+constexpr int kNielsEntries = kTableB;   // radix-256 signed digits: |d| <= 128
+// the level holding 2^(32 q) B: part q (word q) of a 256-bit scalar
+constexpr int kNielsLevelOfPart[8] = {0, 4, 2, 5, 1, 6, 3, 7};
+
+CPZ_HD ge_niels niels_entry(const ge_niels* e) {
+  ge_niels r;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4* s = reinterpret_cast<const uint4*>(e);
+  uint4* d = reinterpret_cast<uint4*>(&r);
+#pragma unroll
+  for (int v = 0; v < (int)(sizeof(ge_niels) / 16); v++) d[v] = s[v];
+#else
+  r = *e;
+#endif
+  return r;
+}
+
+// [d] g and [d] h together from one pair's tables (mixed-pair prover, k_prove_points_pairs).
+// dig: the radix-256 signed digits of d < 2^253 (sc_recode_radix256: 32 bytes in [-128, 127],
+// digit j at weight 2^(8 j), four per word).  Digit 4 q + b sits at weight 2^(8 b) on 2^(32 q) B,
+// so for window b = 3..0: 8 doublings of both sums (none before the first window), then for
+// part q = 0..7 the entry |digit| - 1 of part q's table of g and of h, negated for a negative
+// digit; a zero digit adds nothing.  24 doublings and at most 32 additions per product, one
+// digit decode for both.
+// Lazy sign (as comb_add): each sum is kept as sigma * cur, sigma = the sign of the last
+// non-zero digit; a digit of sign tau adds the stored entry to (sigma tau) * cur.  Doublings
+// commute with the sign, and both sums see the same digits, so they share sigma.
+CPZ_HD void pair_table_mul(ge_p3& G, ge_p3& H, const ge_niels* tab, const uint32_t dig_in[8]) {
+  uint32_t dig[8];
+#pragma unroll
+  for (int q = 0; q < 8; q++) dig[q] = dig_in[q];
+  ge_p1p1 cg = p1p1_identity(), ch = p1p1_identity();
+  int32_t sign = 0;
+#pragma unroll 1
+  for (int b = 3; b >= 0; b--) {
+    if (b != 3) {
+#pragma unroll 1
+      for (int k = 0; k < 8; k++) {
+        cg = p2_dbl(p1p1_to_p2(cg));
+        ch = p2_dbl(p1p1_to_p2(ch));
+      }
+    }
+#pragma unroll 1
+    for (int q = 0; q < 8; q++) {
+      // byte 3 of word 0 is digit 4 q + 3, the top one; the words rotate so that no runtime index
+      // selects a register
+      const uint32_t w = dig[0];
+#pragma unroll
+      for (int t = 0; t < 7; t++) dig[t] = dig[t + 1];
+      dig[7] = w << 8;
+      const int32_t d = (int32_t)w >> 24;
+      if (d == 0) continue;
+      const ge_niels* e = tab + (2 * kNielsLevelOfPart[q]) * kNielsEntries + ((d < 0 ? -d : d) - 1);
+      const ge_niels eg = niels_entry(e), eh = niels_entry(e + kNielsEntries);
+      const int32_t flip = d ^ sign;
+      cg = ge_add_niels(p1p1_to_p3(ge_p1p1_cneg(cg, flip)), eg);
+      ch = ge_add_niels(p1p1_to_p3(ge_p1p1_cneg(ch, flip)), eh);
+      sign = d;
+    }
+  }
+  G = p1p1_to_p3(ge_p1p1_cneg(cg, sign));
+  H = p1p1_to_p3(ge_p1p1_cneg(ch, sign));
+}
+
 // k * B for 1 <= k <= 255 by double-and-add (table construction).
 CPZ_HD ge_p3 small_mul(const ge_p3& B, int k) {
   ge_p3 acc = ge_identity();

@@ -227,6 +227,38 @@ int cpz_prove_device(cpz_ctx *ctx, const uint8_t g[32], const uint8_t h[32], siz
                      const uint8_t *d_ctx_present, void *d_y1, void *d_y2, void *d_r1, void *d_r2, void *d_s,
                      void *stream);
 
+/* The prover with a (g, h) pair per proof, in one call: `pairs` holds npairs host rows of 64
+ * bytes (g then h), pair_idx[i] < npairs names entry i's row, and row i of every output is byte
+ * for byte what cpz_prove writes for (x_i, k_i, context i) under pairs[pair_idx[i]].  Rows of
+ * `pairs` may repeat and may be the default pair.  Every pair is made resident at once from its
+ * 128-entry tables (a pair without cached tables gets a light set, stage 13) and every proof's
+ * four points come from its own pair's tables: 24 doublings and at most 32 additions per point
+ * against the comb's 16 additions, but no comb is ever built by these calls, for any npairs
+ * (1 included) and any n up to CPZ_PROVE_PAIRS_MAX_PROOFS, and there is no chunking.  Kernel
+ * time is reported under stage 6.
+ * Both forms return synchronised.  The device form takes 16-byte aligned device rows and n
+ * device-resident indices (`pairs` stays a host array), on `stream` (a hipStream_t, or NULL for
+ * the context's own stream).  As cpz_verify_each_pairs_device it first scans the indices on the
+ * device and synchronises `stream` to read the result: an offending index is CPZ_EINVAL naming
+ * the lowest such entry, with every output untouched.  It then enqueues the prover and
+ * synchronises `stream` again before it returns.  Any later call on the same context, on any
+ * stream, is ordered after this call's kernels.
+ * Checked before anything is launched (the device form: before anything but the index scan) or
+ * written, in cpz_verify_each_pairs' order, cpz_last_error naming the pair or the entry:
+ * n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_PAIRS_MAX, n > CPZ_PROVE_PAIRS_MAX_PROOFS, a
+ * null pointer, a misaligned device row or a pair_idx[i] >= npairs -> CPZ_EINVAL; a pair that is
+ * the identity, has g == h or does not decode -> CPZ_EGENERATOR. */
+#define CPZ_PROVE_PAIRS_MAX_PROOFS 1048576 /* 1 << 20 */
+int cpz_prove_pairs(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
+                    const uint32_t *pair_idx, const uint8_t *x, const uint8_t *k,
+                    const uint8_t *ctx_bytes, const uint64_t *ctx_off, const uint8_t *ctx_present,
+                    uint8_t *y1, uint8_t *y2, uint8_t *r1, uint8_t *r2, uint8_t *s);
+int cpz_prove_pairs_device(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
+                           const uint32_t *d_pair_idx, const void *d_x, const void *d_k,
+                           const void *d_ctx_bytes, const uint64_t *d_ctx_off,
+                           const uint8_t *d_ctx_present, void *d_y1, void *d_y2, void *d_r1,
+                           void *d_r2, void *d_s, void *stream);
+
 /* Synthetic input generator (Prover::prove_with_transcript, prover/mod.rs:86-131):
  * witness x_i and nonce k_i = from_bytes_mod_order_wide(ChaCha20(seed_x / seed_k, block
  * first_index + i)); writes y1 = x g, y2 = x h, r1 = k g, r2 = k h, s = k + c x. */
