@@ -10,6 +10,9 @@
 * ``tests/native/libcpz_partprobe.so`` -- gfx950 build of csrc/part.hip, included unchanged,
                            behind plain C probes of its kernels (tests/native/partprobe.hip),
                            for the GPU unit tests only; never linked into the product.
+* ``tests/native/libcpz_partpairsprobe.so`` -- the same for part.hip's pair mode
+                           (tests/native/partpairsprobe.hip), for the GPU unit tests only; never
+                           linked into the product.
 * ``tests/native/libcpz_msmprobe.so`` -- gfx950 build of csrc/rlc.hip, included unchanged, behind
                            plain C probes of the MSM's sort and reduction kernels
                            (tests/native/msmprobe.hip), for the GPU unit tests only; never linked
@@ -35,6 +38,7 @@ LIBCPZ = os.path.join(LIBDIR, "libcpz.so")
 HOSTTEST = os.path.join(ROOT, "tests", "native", "libcpz_hosttest.so")
 DEVPROBE = os.path.join(ROOT, "tests", "native", "libcpz_devprobe.so")
 PARTPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partprobe.so")
+PARTPAIRSPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partpairsprobe.so")
 MSMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_msmprobe.so")
 ARCH = os.environ.get("CPZ_OFFLOAD_ARCH", "gfx950")
 
@@ -161,6 +165,22 @@ def build_partprobe(force: bool = False, out: str = PARTPROBE, include: str = CS
     return out
 
 
+def build_partpairsprobe(force: bool = False, out: str = PARTPAIRSPROBE, include: str = CSRC) -> str:
+    """Probes of the partitioned check's pair-mode kernels (tests/native/partpairsprobe.hip, which
+    includes part.hip itself), compiled like the product's units.  `out` / `include` build them
+    over another copy of csrc (a mutated one) for tests/test_gpu_part_pairs_probe.py's
+    CPZ_PARTPAIRSPROBE."""
+    src = os.path.join(ROOT, "tests", "native", "partpairsprobe.hip")
+    deps = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h") or f == "part.hip"]
+    if not force and not _newer(out, [src] + deps):
+        return out
+    tmp = out + ".tmp"
+    _run([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", include,
+          "-I", os.path.join(ROOT, "include"), "-shared", src, "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 def build_msmprobe(force: bool = False, out: str = MSMPROBE, include: str = CSRC) -> str:
     """Probes of the MSM's sort and reduction kernels (tests/native/msmprobe.hip, which includes
     rlc.hip itself), compiled like the product's units.  `out` / `include` build them over
@@ -238,6 +258,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_libcpz(force, verbose)
     build_devprobe(force)
     build_partprobe(force)
+    build_partpairsprobe(force)
     build_msmprobe(force)
     build_cpp_test(force)
     build_dropin_test(force)

@@ -528,7 +528,7 @@ class Gpu:
 
     def verify_batch_pairs(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, seed: bytes,
                            first_index: int = 0, contexts=None, statuses: bool = True,
-                           equations_only: bool = False):
+                           equations_only: bool = False, locate: str = "auto"):
         """RLC batch check where entry i stands under pairs[pair_idx[i]], all in one MSM
         (cpz_verify_batch_pairs_ex): at most PAIRS_MAX pairs and BATCH_PAIRS_MAX_PROOFS proofs.
         Returns (partial: bytes, batch_ok: bool, status: uint8[n] or None) as verify_batch does;
@@ -536,7 +536,13 @@ class Gpu:
         weights keyed by first_index + the entry's position here.  A batch that passes builds no
         table for any pair.  With statuses=True a failing batch runs the fallback search and each
         status is what verify_each_pairs returns for that entry.  pair_idx: n integers in
-        [0, len(pairs)), checked here before the library is called."""
+        [0, len(pairs)), checked here before the library is called.
+        locate: "auto" (bisection, with the partitioned check for large dense ranges) or
+        "partitioned" (CPZ_CALL_PARTITIONED: a failing batch goes to the partitioned check at
+        once, for callers who expect more invalid entries than bisection can prune)."""
+        if locate not in ("auto", "partitioned"):
+            raise InvalidParams("locate must be \"auto\" or \"partitioned\", not %r" % (locate,))
+        flags = _flags(equations_only) | (_native.CALL_PARTITIONED if locate == "partitioned" else 0)
         n = len(y1)
         npairs = len(pairs)
         idx = _pair_indices(pair_idx, n, npairs)
@@ -547,7 +553,7 @@ class Gpu:
         ok = ctypes.c_int(0)
         out = np.empty(n, dtype=np.uint8) if statuses else None
         _native.check(self._lib.cpz_verify_batch_pairs_ex(
-            self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
+            self._h, flags, npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
             _ptr(off), _ptr(present), bytes(seed), first_index, partial, ctypes.byref(ok), _ptr(out)))
         return partial.raw, bool(ok.value), out
 

@@ -255,7 +255,10 @@ hipError_t launch_verify_wide_pairs(const VerifyArgs& a, const ChallengeArgs& ca
 // The eight-lane kernel with a pair per proof (k_verify_quad_pairs): at most a.quad_max proofs,
 // a.c / a.status from launch_challenge_pairs, every proof's generator tables from its own pair's
 // descriptor as variable bases; a.comb / a.vtab / a.vtab16 are unused.  a.scratch as for
-// k_verify_quad (kQuadProofScratch bytes per proof).
+// k_verify_quad (kQuadProofScratch bytes per proof).  With a.blocks: the listed blocks of
+// a.block_proofs proofs each of a prepared mixed-pair batch (at most a.quad_max slots; rows, a.c,
+// a.status and pa.pair_idx are the whole batch's): a.status holds the prepare's decode-level
+// statuses, entries with a non-zero one keep it and every other ends with its per-proof status.
 hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hipStream_t st);
 // Device-resident indices of a mixed-pair call against npairs: *first (set to kPairIdxOk by the
 // caller, on the same stream) ends as the lowest i with idx[i] >= npairs, or stays kPairIdxOk.

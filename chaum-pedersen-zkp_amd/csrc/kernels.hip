@@ -804,6 +804,9 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
   }
   if (i >= a.n) return;                          // a proof's eight lanes together
   if (kPre && a.status[i] != kStOk) return;      // decode-level rejection: already final
+  // listed blocks of a mixed-pair batch check (runtime.hip, pairs_part): the statuses are the
+  // prepare's decode-level ones, final where non-zero; the others had a clean response status
+  if (kPairs && a.blocks && a.status[i] != kStOk) return;
 #if defined(CPZ_CLOCK_PROBE)
   // timing builds only: shader-clock stamps at the phase boundaries of block 0's first proof
   uint64_t stamp[kQuadPhases];
@@ -950,12 +953,17 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
 }
 
 // k_challenge_pairs' challenges and response statuses in a.c / a.status; at most a.quad_max
-// proofs (the slab holds kQuadProofScratch bytes of tables for each).
+// proofs (the slab holds kQuadProofScratch bytes of tables for each).  With a.blocks: the listed
+// blocks of a.block_proofs proofs each of a prepared mixed-pair batch (a.nblocks of them, at most
+// a.quad_max slots; rows, a.c, a.status and pa.pair_idx are the whole batch's, a.n its size) --
+// a.status holds the prepare's decode-level statuses and entries with a non-zero one keep it.
 hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hipStream_t st) {
-  if (a.n <= 0) return hipSuccess;
-  if (a.pre || a.blocks || !a.c || !a.status || !a.scratch || !pa.desc || !pa.pair_idx || a.n > a.quad_max)
+  if (a.n <= 0 || (a.blocks && a.nblocks <= 0)) return hipSuccess;
+  if (a.blocks && a.block_proofs < 1) return hipErrorInvalidValue;
+  const int64_t slots = a.blocks ? a.nblocks * (int64_t)a.block_proofs : a.n;
+  if (a.pre || !a.c || !a.status || !a.scratch || !pa.desc || !pa.pair_idx || slots > a.quad_max)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_verify_quad<false, true, true>), dim3((unsigned)((a.n + 31) / 32)), dim3(256), 0, st, a, pa);
+  hipLaunchKernelGGL((k_verify_quad<false, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a, pa);
   return hipGetLastError();
 }
 

@@ -59,12 +59,44 @@ __device__ __forceinline__ int digit16(const uint2& g, int q) {
   return (int)(int16_t)(uint16_t)(w >> (16 * (q & 1)));
 }
 
+// The sum mod l of up to kPartProofs canonical scalars (pair mode: a pair's products within a
+// block): a 288-bit accumulator, reduced once.
+struct ScSum {
+  uint32_t w[9];
+};
+__device__ __forceinline__ void scsum_add(ScSum& a, const sc& x) {
+  uint64_t c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    c += (uint64_t)a.w[i] + x.w[i];
+    a.w[i] = (uint32_t)c;
+    c >>= 32;
+  }
+  a.w[8] += (uint32_t)c;
+}
+__device__ __forceinline__ sc scsum_reduce(const ScSum& a) {
+  uint32_t x[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) x[i] = i < 9 ? a.w[i] : 0u;
+  return sc_reduce_wide(x);
+}
+
 // ---------------------------------------------------------------------------------------
 // k_part_sort: thread t holds proof t's four points (prepared order -r1, -y1, -r2, -y2),
 // threads 0 / 1 also g / h with the block's weight sums (ids 4 kPartProofs, + 1).
+// kPairs (k_part_sort_pairs, a mixed-pair batch): the extras are the block's pairs' points, thread
+// u < 2 npairs holding extra u = 2 p + k (id 4 kPartProofs + u): gh[u] with the sum of prod[2 i + k]
+// over the block's proofs under pair p, which the thread adds up from the block's products and
+// indices staged in LDS (or reads, in the locate pass: PartArgs::pair_idx null).  A pair without an
+// entry in the block, or whose sum is 0, has zero digits and so no list entry.  kPairs is a
+// constant, so k_part_sort keeps its code.
 // ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kPartProofs) k_part_sort(PartArgs a) {
+template <bool kPairs>
+__device__ __forceinline__ void part_sort_body(const PartArgs& a) {
   constexpr int kT = kPartProofs;  // threads: one per proof of the block
+  constexpr int kListCap = kPairs ? kPartListCapPairs : kPartListCap;
+  __shared__ sc sprod[kPairs ? 2 * kPartProofs : 1];     // (pair mode only: unused, and so not
+  __shared__ uint32_t spair[kPairs ? kPartProofs : 1];   //  allocated, without it)
   __shared__ uint32_t cur[kPartWindows][kPartBuckets];
   __shared__ uint32_t wtot[kPartWindows];
   __shared__ uint32_t wbase[kPartWindows + 1];
@@ -77,7 +109,44 @@ __global__ void __launch_bounds__(kPartProofs) k_part_sort(PartArgs a) {
   const int64_t j0 = 4 * pi;
   const bool in = pi < a.n;  // past the batch's end (last block): no entries
   int16_t ex[kRlcWindows];
-  if (t < 2) {  // the block's sum of a s (t = 0) / b s (t = 1): its one or two block sums
+  const int nex = kPairs ? 2 * a.npairs : 2;  // threads holding an extra
+  // pair mode: extra t's digits, [window][thread], over the products once they are summed (a
+  // dynamically indexed register array of them went to scratch)
+  int16_t* sex = reinterpret_cast<int16_t*>(sprod);
+  if constexpr (kPairs) {
+    sc s;
+#pragma unroll
+    for (int k = 0; k < 8; k++) s.w[k] = 0;
+    if (a.pair_idx) {
+      sprod[2 * t] = s;  // past the end: zero, never read from a.prod
+      sprod[2 * t + 1] = s;
+      if (in) {
+        sprod[2 * t] = a.prod[2 * pi];
+        sprod[2 * t + 1] = a.prod[2 * pi + 1];
+      }
+      spair[t] = in ? a.pair_idx[pi] : 0xffffffffu;  // past the end: no pair
+      __syncthreads();
+      if (t < nex) {
+        const uint32_t p = (uint32_t)t >> 1;
+        ScSum acc;
+#pragma unroll
+        for (int k = 0; k < 9; k++) acc.w[k] = 0;
+#pragma unroll 1
+        for (int u = 0; u < kT; u++)
+          if (spair[u] == p) scsum_add(acc, sprod[2 * u + (t & 1)]);
+        s = scsum_reduce(acc);
+      }
+      __syncthreads();
+    } else if (t < nex) {
+      s = a.prod[(int64_t)nex * gb + t];
+    }
+    if (t < nex) {
+      int16_t d[kRlcWindows];
+      recode16(d, s.w);
+#pragma unroll
+      for (int w = 0; w < kRlcWindows; w++) sex[w * kT + t] = d[w];
+    }
+  } else if (t < 2) {  // the block's sum of a s (t = 0) / b s (t = 1): its one or two block sums
     constexpr int R = kPartProofs / kRlcSumBlock;
     sc s = a.block_sums[2 * (R * gb) + t];
 #pragma unroll
@@ -95,9 +164,9 @@ __global__ void __launch_bounds__(kPartProofs) k_part_sort(PartArgs a) {
       if (lo) atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u);
       if (hi) atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u);
     }
-    if (t < 2) {
+    if (t < nex) {
       int lo, hi;
-      split8(ex[w], lo, hi);
+      split8(kPairs ? (int)sex[w * kT + t] : (int)ex[w], lo, hi);
       if (lo) atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u);
       if (hi) atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u);
     }
@@ -174,7 +243,7 @@ __global__ void __launch_bounds__(kPartProofs) k_part_sort(PartArgs a) {
   __syncthreads();
   for (int i = t; i < kPartWindows * kPartBuckets; i += kT) (&cur[0][0])[i] += wbase[i / kPartBuckets];
   __syncthreads();
-  uint16_t* list = a.lists + b * kPartListCap;
+  uint16_t* list = a.lists + b * kListCap;
 #pragma unroll 1
   for (int w = 0; w < kRlcWindows; w++) {
     const uint2 g = in ? *reinterpret_cast<const uint2*>(a.digits + w * a.dstride + j0) : make_uint2(0u, 0u);
@@ -186,15 +255,18 @@ __global__ void __launch_bounds__(kPartProofs) k_part_sort(PartArgs a) {
       if (lo) list[atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u)] = id | (lo < 0 ? 0x8000 : 0);
       if (hi) list[atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u)] = id | (hi < 0 ? 0x8000 : 0);
     }
-    if (t < 2) {
+    if (t < nex) {
       int lo, hi;
-      split8(ex[w], lo, hi);
+      split8(kPairs ? (int)sex[w * kT + t] : (int)ex[w], lo, hi);
       const uint16_t id = (uint16_t)(4 * kPartProofs + t);
       if (lo) list[atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u)] = id | (lo < 0 ? 0x8000 : 0);
       if (hi) list[atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u)] = id | (hi < 0 ? 0x8000 : 0);
     }
   }
 }
+
+__global__ void __launch_bounds__(kPartProofs) k_part_sort(PartArgs a) { part_sort_body<false>(a); }
+__global__ void __launch_bounds__(kPartProofs) k_part_sort_pairs(PartArgs a) { part_sort_body<true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // k_part_acc
@@ -220,9 +292,13 @@ __device__ __forceinline__ ge_p3 p3_select(const ge_p3& x, const ge_p3& y, bool 
 // current step's arithmetic runs, so the prefetch costs no VGPRs (the kernel sits at the
 // 256-VGPR budget of 2 waves per SIMD).  The vmcnt wait at the top of a step waits for that
 // prefetch and the id prefetch (and, once per lane, the stores of its first window's sums).
+// The only place that picks an extra's source: g / h of the tables, or (kPairs) the pairs' points.
+template <bool kPairs>
 __device__ __forceinline__ void part_stage(uint4 (*slot)[64], const PartArgs& a, const ge_niels* P, uint32_t id) {
   const uint32_t j = id & 0x7fffu;
-  const ge_niels* src = j < 4u * kPartProofs ? P + j : a.tab + (j == 4u * kPartProofs ? 0 : kNielsEntriesRlc);
+  const ge_niels* src = j < 4u * kPartProofs ? P + j
+                        : kPairs             ? a.gh + (j - 4u * kPartProofs)
+                                             : a.tab + (j == 4u * kPartProofs ? 0 : kNielsEntriesRlc);
   const uint4* g = reinterpret_cast<const uint4*>(src);
 #pragma unroll
   for (int v = 0; v < 8; v++) __builtin_amdgcn_global_load_lds(g + v, &slot[v][0], 16, 0, 0);
@@ -261,7 +337,8 @@ __device__ __forceinline__ fe acc_load_z(uint4 (*az)[64], int lane) {
   return r;
 }
 
-__global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) {
+template <bool kPairs>
+__device__ __forceinline__ void part_acc_body(const PartArgs& a) {
   __shared__ uint4 lds[4][19][64];  // per wave: staged point (0..7), acc (8..15), acc's Z (16..18)
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + wv;
@@ -271,7 +348,7 @@ __global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) {
   const int64_t gb = a.blk0 + b;
   const uint32_t units = a.assign[b * kPartUnits + lane];  // (low unit, high unit), k_part_sort
   int v = (units & 0xff) >> 2, h = units & 3;
-  const uint16_t* list = a.lists + b * kPartListCap;
+  const uint16_t* list = a.lists + b * (kPairs ? kPartListCapPairs : kPartListCap);
   const uint16_t* ob = a.offs + b * kPartOffs;
   const ge_niels* P = a.pts + (int64_t)4 * kPartProofs * (a.pmap ? (int64_t)a.pmap[gb] : gb);
   ge_p3* ws = a.wsum + gb * kPartWsum;  // indexed by the global block: one combine pass for all chunks
@@ -281,7 +358,7 @@ __global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) {
   uint32_t e = o[k], eend = o[k + 1], elast = o[klo + width];
   uint32_t cid = e < elast ? list[e] : 0u;
   uint32_t nid = e + 1 < elast ? list[e + 1] : 0u;
-  if (e < eend) part_stage(slot, a, P, cid);
+  if (e < eend) part_stage<kPairs>(slot, a, P, cid);
   ge_p3 run = ge_identity();
   uint4 (*an)[64] = lds[wv] + 8;   // acc's Y+X, Y-X, 2dT (the staged points' layout)
   uint4 (*az)[64] = lds[wv] + 16;  // acc's Z
@@ -333,7 +410,7 @@ __global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) {
       k2 = k + 1;
       eend2 = o[k2 + 1];
     }
-    if (!wend && e2 < eend2) part_stage(slot, a, P, cid2);
+    if (!wend && e2 < eend2) part_stage<kPairs>(slot, a, P, cid2);
     {
       ge_cached oc;
       oc.YpX = q.ypx;
@@ -363,7 +440,7 @@ __global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) {
       elast = o[klo + width];
       cid2 = e2 < elast ? list[e2] : 0u;
       nid2 = e2 + 1 < elast ? list[e2 + 1] : 0u;
-      if (e2 < eend2) part_stage(slot, a, P, cid2);
+      if (e2 < eend2) part_stage<kPairs>(slot, a, P, cid2);
       run = ge_identity();
       acc_store(an, az, lane, ge_cached_identity());
     }
@@ -374,6 +451,9 @@ __global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) {
     nid = nid2;
   }
 }
+
+__global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) { part_acc_body<false>(a); }
+__global__ void __launch_bounds__(256, 2) k_part_acc_pairs(PartArgs a) { part_acc_body<true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // k_part_combine: quad j of the wave owns block 16 x blockIdx + j.
@@ -563,7 +643,11 @@ __device__ __forceinline__ void index_weight_digits(int16_t d[kRlcWindows], cons
   for (int w = 9; w < kRlcWindows; w++) d[w] = 0;
 }
 
-__global__ void __launch_bounds__(kPartProofs) k_part_index_digits(PartIdxArgs a) {
+// kPairs (k_part_index_digits_pairs): the same digits; the sums are per pair -- thread t parks
+// j_t prod[2 i], j_t prod[2 i + 1] (the prepare's products: zero where it gave zero weight) and its
+// pair in LDS, thread u < 2 npairs adds up extra u's and writes it to pair_sums, compact.
+template <bool kPairs>
+__device__ __forceinline__ void part_index_digits_body(const PartIdxArgs& a) {
   static_assert(kPartLocJ0 < (1 << 16) - 258 && kPartLocJ0 - 2 * (kPartProofs - 1) > (1 << 15),
                 "index multipliers: digit 8 of j a below 2^15 - 128, and above 2^15 so that it spreads");
   __shared__ sc red_a[kPartProofs];
@@ -579,6 +663,8 @@ __global__ void __launch_bounds__(kPartProofs) k_part_index_digits(PartIdxArgs a
   red_a[t] = zero;
   red_b[t] = zero;
   const bool live = i < a.n && a.status[i] == kStOk;
+  __shared__ uint32_t spair[kPairs ? kPartProofs : 1];  // (pair mode only)
+  if constexpr (kPairs) spair[t] = i < a.n ? a.pair_idx[i] : 0xffffffffu;
   uint32_t blk[16];
   if (live) chacha20_block(blk, a.seed, a.first_index + (uint64_t)i, 0);
   sc J = zero;
@@ -596,15 +682,33 @@ __global__ void __launch_bounds__(kPartProofs) k_part_index_digits(PartIdxArgs a
         recode16(d, sc_mul(J, sc_mul(rlc_weight(u), c)).w);
       } else {
         index_weight_digits(d, u, j);
-        sc sv;
-        rlc_load8(sv.w, a.s, i);
-        (q == 0 ? red_a : red_b)[t] = sc_mul(J, sc_mul(rlc_weight(u), sv));
+        if constexpr (kPairs) {
+          (q == 0 ? red_a : red_b)[t] = sc_mul(J, a.prod[2 * i + (q >> 1)]);
+        } else {
+          sc sv;
+          rlc_load8(sv.w, a.s, i);
+          (q == 0 ? red_a : red_b)[t] = sc_mul(J, sc_mul(rlc_weight(u), sv));
+        }
       }
     }
 #pragma unroll
     for (int w = 0; w < kRlcWindows; w++) a.digits[(int64_t)w * a.dstride + 4 * o + q] = d[w];
   }
   __syncthreads();
+  if constexpr (kPairs) {
+    if (t < 2 * a.npairs) {
+      const uint32_t p = (uint32_t)t >> 1;
+      const sc* red = (t & 1) ? red_b : red_a;
+      ScSum acc;
+#pragma unroll
+      for (int k = 0; k < 9; k++) acc.w[k] = 0;
+#pragma unroll 1
+      for (int u = 0; u < kPartProofs; u++)
+        if (spair[u] == p) scsum_add(acc, red[u]);
+      a.pair_sums[(int64_t)2 * a.npairs * b + t] = scsum_reduce(acc);
+    }
+    return;
+  }
   for (int off = kRlcSumBlock / 2; off > 0; off >>= 1) {
     if ((t % kRlcSumBlock) < off) {
       red_a[t] = sc_add(red_a[t], red_a[t + off]);
@@ -617,6 +721,11 @@ __global__ void __launch_bounds__(kPartProofs) k_part_index_digits(PartIdxArgs a
     a.block_sums[2 * sb] = red_a[t];
     a.block_sums[2 * sb + 1] = red_b[t];
   }
+}
+
+__global__ void __launch_bounds__(kPartProofs) k_part_index_digits(PartIdxArgs a) { part_index_digits_body<false>(a); }
+__global__ void __launch_bounds__(kPartProofs) k_part_index_digits_pairs(PartIdxArgs a) {
+  part_index_digits_body<true>(a);
 }
 
 // [k] P for a small k > 0 (double and add from the top bit).
@@ -672,7 +781,12 @@ __global__ void __launch_bounds__(256) k_gather_status(const uint8_t* status, co
 
 hipError_t launch_part_index_digits(const PartIdxArgs& a, hipStream_t st) {
   if (a.nblk <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_part_index_digits, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  if (a.prod) {
+    if (!a.pair_idx || !a.pair_sums || a.npairs < 1 || a.npairs > kPartMaxPairs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_part_index_digits_pairs, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(k_part_index_digits, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  }
   return hipGetLastError();
 }
 
@@ -692,13 +806,21 @@ hipError_t launch_gather_status(const uint8_t* status, const uint32_t* idx, int6
 
 hipError_t launch_part_sort(const PartArgs& a, hipStream_t st) {
   if (a.nblk <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_part_sort, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  if (a.prod) {
+    if (!a.gh || a.npairs < 1 || a.npairs > kPartMaxPairs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_part_sort_pairs, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  } else {
+    hipLaunchKernelGGL(k_part_sort, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  }
   return hipGetLastError();
 }
 
 hipError_t launch_part_acc(const PartArgs& a, hipStream_t st) {
   if (a.nblk <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_part_acc, dim3((unsigned)((a.nblk + 3) / 4)), dim3(256), 0, st, a);
+  if (a.prod)
+    hipLaunchKernelGGL(k_part_acc_pairs, dim3((unsigned)((a.nblk + 3) / 4)), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_part_acc, dim3((unsigned)((a.nblk + 3) / 4)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -118,6 +118,14 @@ constexpr int kPartBuckets = 128;                     // |digit| in [1, 128]
 constexpr int kPartQuarters = 4;                      // lanes per window pair (32 buckets each)
 constexpr int kPartTopBuckets = 16;                   // |digit| bound of the top window (part.hip)
 constexpr int kPartListCap = kPartWindows * kPartPoints;  // sorted entries per block, at most
+// Pair mode (PartArgs::prod): a block's extras are its pairs' g_p, h_p -- up to 2 kPartMaxPairs of
+// them (CPZ_PAIRS_MAX of cpz.h; runtime.hip asserts the two agree), ids 4 kPartProofs + 2 p + k --
+// and its launches have a list stride of their own.
+constexpr int kPartMaxPairs = 64;
+constexpr int kPartListCapPairs = kPartWindows * (4 * kPartProofs + 2 * kPartMaxPairs);
+static_assert(kPartListCapPairs <= 0xffff, "pair mode: a block's list offsets are 16-bit");
+static_assert(4 * kPartProofs + 2 * kPartMaxPairs <= 0x8000, "pair mode: point ids take 15 bits (bit 15: negate)");
+static_assert(2 * kPartMaxPairs <= kPartProofs, "pair mode: one sort thread per extra");
 constexpr int kPartOffs = kPartWindows * (kPartBuckets + 1);
 constexpr int kPartWsum = kPartWindows * kPartQuarters * 2;  // (W, S) per window and quarter
 constexpr int kPartUnits = kPartWindows * kPartQuarters / 2;  // walk units per half (64 = lanes)
@@ -157,6 +165,15 @@ struct PartArgs {
   const uint32_t* pmap = nullptr;  // locate pass: listed block b's points are those of prepared
                                    // block pmap[b] (digits, sums and outputs are compact)
   uint64_t* clock_probe = nullptr;  // CPZ_CLOCK_PROBE builds only: k_part_acc, 5 words per wave
+  // Pair mode (a mixed-pair batch; null prod: the single-pair mode above).  block_sums and tab are
+  // unused, lists has a stride of kPartListCapPairs, and block b's extras are gh[2 p + k] (id
+  // 4 kPartProofs + 2 p + k) with the sum mod l of prod[2 i + k] over the block's proofs i < n
+  // with pair_idx[i] == p; rows at or beyond n are never read.  Null pair_idx (the locate pass):
+  // prod holds the sums themselves, [blocks][2 npairs], compact (k_part_index_digits_pairs).
+  const sc* prod = nullptr;            // [n][2] a_i s_i, b_i s_i (RlcPrepArgs::prod)
+  const uint32_t* pair_idx = nullptr;  // [n]
+  const ge_niels* gh = nullptr;        // pair p's affine Niels points at gh[2 p], gh[2 p + 1] (k_pair_setup)
+  int npairs = 0;
 };
 
 // ---- locating a failing block's forged entry (part.hip) ----------------------------------
@@ -191,6 +208,12 @@ struct PartIdxArgs {
   int16_t* digits;               // [16][dstride] compact: listed block b's proof t at 4 (kPartProofs b + t)
   int64_t dstride;
   sc* block_sums;                // [nblk * kPartProofs / kRlcSumBlock][2], compact
+  // Pair mode (null prod: the single-pair mode above): block_sums is unused; listed block b's
+  // sums over its proofs under pair p of j_t prod[2 i + k] go to pair_sums[(b npairs + p) 2 + k].
+  const sc* prod = nullptr;            // [n][2] of the prepared batch
+  const uint32_t* pair_idx = nullptr;  // [n]
+  int npairs = 0;
+  sc* pair_sums = nullptr;             // [nblk][npairs][2], compact
 };
 
 struct PartLocArgs {

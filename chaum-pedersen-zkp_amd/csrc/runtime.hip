@@ -1342,12 +1342,24 @@ void part_release(cpz_ctx* ctx) {
 // Fills `cand` with the located proofs and leaves in `whole` the blocks to verify per proof.
 // Its buffers (16 KB of digits per failing block) are taken on demand; if they do not fit,
 // every failing block is verified per proof, as without the pass.
+// px (a range of a mixed-pair batch, pairs_part): the prepared points, challenges, products and
+// indices of the range (n, s, d_status and first_index are the range's too, blocks count from its
+// start), and the sums are per pair (PartIdxArgs::pair_sums -> PartArgs::prod).
+struct PartPairs {
+  const cpz::ge_niels* pts;
+  const uint32_t* c;
+  const cpz::sc* prod;
+  const uint32_t* pair_idx;
+  const cpz::ge_niels* gh;
+  int npairs;
+};
+
 int part_locate(cpz_ctx* ctx, int64_t n, const void* s, const uint8_t* d_status, const uint8_t seed[32],
                 uint64_t first_index, const std::vector<uint32_t>& blocks, std::vector<uint32_t>& whole,
-                std::vector<uint32_t>& cand, hipStream_t st) {
+                std::vector<uint32_t>& cand, hipStream_t st, const PartPairs* px = nullptr) {
   const int64_t nf = (int64_t)blocks.size();
   const int64_t dstride = ((4 * cpz::kPartProofs * nf) + 7) & ~(int64_t)7;
-  const int64_t nsum = nf * (cpz::kPartProofs / cpz::kRlcSumBlock);
+  const int64_t nsum = px ? nf * px->npairs : nf * (cpz::kPartProofs / cpz::kRlcSumBlock);
   if (ctx->pt_ldig.ensure((size_t)cpz::kRlcWindows * dstride * sizeof(int16_t)) != hipSuccess ||
       ctx->pt_lsum.ensure((size_t)2 * nsum * sizeof(cpz::sc)) != hipSuccess ||
       ctx->pt_lpart.ensure((size_t)nf * sizeof(cpz::ge_p3)) != hipSuccess ||
@@ -1366,20 +1378,32 @@ int part_locate(cpz_ctx* ctx, int64_t n, const void* s, const uint8_t* d_status,
     ia.first_index = first_index;
     std::memcpy(ia.seed, seed, 32);
     ia.s = static_cast<const uint32_t*>(s);
-    ia.c = static_cast<const uint32_t*>(ctx->c.p);
+    ia.c = px ? px->c : static_cast<const uint32_t*>(ctx->c.p);
     ia.status = d_status;
     ia.digits = static_cast<int16_t*>(ctx->pt_ldig.p);
     ia.dstride = dstride;
     ia.block_sums = static_cast<cpz::sc*>(ctx->pt_lsum.p);
+    if (px) {
+      ia.prod = px->prod;
+      ia.pair_idx = px->pair_idx;
+      ia.npairs = px->npairs;
+      ia.pair_sums = ia.block_sums;
+    }
     CPZ_HIP(cpz::launch_part_index_digits(ia, st));
     cpz::PartArgs pa;
     pa.n = nf * cpz::kPartProofs;  // compact; proofs past the batch's end have zero digits
-    pa.pts = static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p);
+    pa.pts = px ? px->pts : static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p);
     pa.pmap = d_blocks;
     pa.digits = ia.digits;
     pa.dstride = dstride;
     pa.block_sums = ia.block_sums;
-    pa.tab = static_cast<const cpz::ge_niels*>(ctx->gs->tab.p);
+    if (px) {  // the sums themselves, per listed block and pair (null pair_idx)
+      pa.prod = ia.pair_sums;
+      pa.gh = px->gh;
+      pa.npairs = px->npairs;
+    } else {
+      pa.tab = static_cast<const cpz::ge_niels*>(ctx->gs->tab.p);
+    }
     pa.lists = static_cast<uint16_t*>(ctx->pt_lists.p);
     pa.assign = static_cast<uint16_t*>(ctx->pt_assign.p);
     pa.offs = static_cast<uint16_t*>(ctx->pt_offs.p);
@@ -1409,14 +1433,14 @@ int part_locate(cpz_ctx* ctx, int64_t n, const void* s, const uint8_t* d_status,
   std::vector<uint16_t> loc((size_t)nf);
   CPZ_HIP(hipMemcpyAsync(loc.data(), ctx->pt_loc.p, (size_t)nf * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
   CPZ_HIP(hipStreamSynchronize(st));
-  ctx->fb_stats[6] = (uint64_t)nf;
+  ctx->fb_stats[6] += (uint64_t)nf;  // (a mixed-pair batch: once per range)
   whole.clear();
   for (int64_t k = 0; k < nf; k++) {
     const int64_t e = (int64_t)blocks[(size_t)k] * cpz::kPartProofs + loc[(size_t)k];
     if (loc[(size_t)k] == cpz::kPartNoLoc || e >= n) whole.push_back(blocks[(size_t)k]);  // (past the end: w.o.p. never)
     else cand.push_back((uint32_t)e);
   }
-  ctx->fb_stats[7] = (uint64_t)cand.size();
+  ctx->fb_stats[7] += (uint64_t)cand.size();
   return CPZ_OK;
 }
 
@@ -2741,6 +2765,8 @@ struct PairBatch {
   const uint32_t* d_idx = nullptr;        // device: n indices
   uint8_t* d_status = nullptr;
   const cpz::PairDesc* d_full = nullptr;  // device descriptors with tables, set at the first leaf
+  const uint8_t* seed = nullptr;          // the weights' keys (the partitioned search's locate pass)
+  uint64_t first_index = 0;
 };
 
 // The MSM over proofs [lo, hi) (lo a multiple of kRlcPrepBlock) of the prepared mixed-pair batch:
@@ -2769,7 +2795,7 @@ int pairs_range_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi,
 // device: up to CPZ_PAIRS_MAX_PROOFS the mixed-pair latency kernels, above (a range most of whose
 // parts failed) the chunked eight-lane path of cpz_verify_each_pairs_bulk.  The first leaf makes
 // the call's pairs resident (light sets unless a full one is cached).
-int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
+int pairs_resident(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
   if (!b.d_full) {
     std::vector<cpz::PairDesc> full(b.npairs);
     for (size_t p = 0; p < b.npairs; p++) {
@@ -2782,6 +2808,11 @@ int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t s
     CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `full` goes
     b.d_full = static_cast<const cpz::PairDesc*>(ctx->bp_desc.p);
   }
+  return CPZ_OK;
+}
+
+int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
+  if (int rc = pairs_resident(ctx, b, st)) return rc;
   ctx->fb_stats[4] += (uint64_t)(hi - lo);
   // a dense range: the chunked eight-lane path (CPZ_PAIRS_LEAF_QUAD=0 in the environment, read at
   // every call, restores the serial latency launches: for measurement, tools/pairs_bulk_ab.py)
@@ -2833,6 +2864,205 @@ int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t s
   return CPZ_OK;
 }
 
+// Per-proof verification (the eight-lane mixed-pair kernel) of `nb` listed blocks of block_proofs
+// proofs each of the prepared batch, d_list on the device: launches of at most verify_quad_max(ctx)
+// slots, alternating over the verify streams and their slabs (launch_quad_pairs_chunks).  The
+// challenges are the batch's (ctx->c); entries with a non-zero decode-level status keep it.
+int pairs_verify_listed(cpz_ctx* ctx, const PairBatch& b, const uint32_t* d_list, int64_t nb, int block_proofs,
+                        hipStream_t st) {
+  if (nb <= 0) return CPZ_OK;
+  const int64_t per = verify_quad_max(ctx) / block_proofs;  // listed blocks per launch
+  if (per < 1) return fail(CPZ_EINVAL, "internal: no room for the eight-lane kernel's tables");
+  const size_t slab = verify_slab_bytes(ctx);
+  const int64_t chunks = (nb + per - 1) / per;
+  const int nst = (int)std::min<int64_t>(CPZ_VERIFY_STREAMS, chunks);
+  CPZ_HIP(ctx->scratch.ensure((size_t)CPZ_VERIFY_STREAMS * slab));
+  if (nst > 1) {
+    if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
+    CPZ_HIP(hipEventRecord(ctx->aux_start, st));
+    for (int k = 0; k < nst - 1; k++) {
+      if (!ctx->aux_stream[k]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[k], ctx->cus, ctx->device, &ctx->own_queues));
+      if (!ctx->aux_done[k]) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_done[k], hipEventDisableTiming));
+      CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->aux_start, 0));
+    }
+  }
+  cpz::VerifyArgs va{};
+  va.n = b.n;
+  va.y1 = static_cast<const uint32_t*>(b.rows[0]);
+  va.y2 = static_cast<const uint32_t*>(b.rows[1]);
+  va.r1 = static_cast<const uint32_t*>(b.rows[2]);
+  va.r2 = static_cast<const uint32_t*>(b.rows[3]);
+  va.s = static_cast<const uint32_t*>(b.rows[4]);
+  va.c = static_cast<const uint32_t*>(ctx->c.p);
+  va.status = b.d_status;
+  va.eq_only = ctx->call_eq ? 1 : 0;
+  va.quad_max = verify_quad_max(ctx);
+  va.block_proofs = block_proofs;
+  cpz::PairArgs pa;
+  pa.desc = b.d_full;
+  pa.pair_idx = b.d_idx;
+  for (int64_t c = 0; c < chunks; c++) {
+    const int k = (int)(c % nst);  // stream k owns scratch slab k
+    hipStream_t sc = k == 0 ? st : ctx->aux_stream[k - 1];
+    cpz::VerifyArgs v = va;
+    v.blocks = d_list + c * per;
+    v.nblocks = std::min<int64_t>(per, nb - c * per);
+    v.scratch = static_cast<char*>(ctx->scratch.p) + (size_t)k * slab;
+    StageTimer t(ctx, 1, sc);
+    CPZ_HIP(cpz::launch_verify_quad_pairs(v, pa, sc));
+  }
+  if (nst > 1) return join_verify_streams(ctx, st);
+  return CPZ_OK;
+}
+
+static_assert(cpz::kPartMaxPairs == CPZ_PAIRS_MAX, "part.hip's pair-mode list stride follows CPZ_PAIRS_MAX");
+
+// The partitioned search over proofs [lo, hi) of a failing mixed-pair batch (lo a multiple of
+// kRlcPrepBlock): every 128-proof block's partial from the pair-mode sort and walk (part.hip) over
+// the prepared points, with the block's own per-pair sums on its pairs' points.  More than half of
+// the blocks failing: the range is verified per proof as pairs_leaf does (the dense path).
+// Otherwise the locate pass over the failing blocks, then per-proof verification, under each
+// entry's own pair, of the located entries and of the blocks not located (part_locate,
+// part_verify_lists); a located entry that verifies sends its whole block there too.
+// The block pass of pairs_part over proofs [lo, hi) on stream `sc`: buffers, the pair-mode sort
+// and walk, the combine.  The blocks count from lo; px receives the range's views.
+int pairs_part_pass(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi, hipStream_t sc, PartPairs& px,
+                    bool timed) {
+  const int64_t n = hi - lo;
+  const int64_t nblk = (n + cpz::kPartProofs - 1) / cpz::kPartProofs;
+  CPZ_HIP(ctx->pt_lists.ensure((size_t)nblk * cpz::kPartListCapPairs * sizeof(uint16_t)));
+  CPZ_HIP(ctx->pt_assign.ensure((size_t)nblk * cpz::kPartUnits * sizeof(uint16_t)));
+  CPZ_HIP(ctx->pt_offs.ensure((size_t)nblk * cpz::kPartOffs * sizeof(uint16_t)));
+  CPZ_HIP(ctx->pt_wsum.ensure((size_t)nblk * cpz::kPartWsum * sizeof(cpz::ge_p3)));
+  CPZ_HIP(ctx->pt_part.ensure((size_t)nblk * sizeof(cpz::ge_p3)));
+  CPZ_HIP(ctx->pt_fail.ensure((size_t)nblk));
+  CPZ_HIP(ctx->pt_blocks.ensure((size_t)2 * nblk * sizeof(uint32_t)));
+  px.pts = static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p) + 4 * lo;
+  px.c = static_cast<const uint32_t*>(ctx->c.p) + 8 * lo;
+  px.prod = static_cast<const cpz::sc*>(ctx->rl_prep.prod.p) + 2 * lo;
+  px.pair_idx = b.d_idx + lo;
+  px.gh = static_cast<const cpz::ge_niels*>(ctx->bp_pts.p);
+  px.npairs = (int)b.npairs;
+  cpz::PartArgs pa;
+  pa.n = n;
+  pa.pts = px.pts;
+  pa.digits = static_cast<const int16_t*>(ctx->rl_prep.dig.p) + 4 * lo;
+  pa.dstride = rlc_dstride(ctx->rl_prep.cap);
+  pa.prod = px.prod;
+  pa.pair_idx = px.pair_idx;
+  pa.gh = px.gh;
+  pa.npairs = px.npairs;
+  pa.lists = static_cast<uint16_t*>(ctx->pt_lists.p);
+  pa.assign = static_cast<uint16_t*>(ctx->pt_assign.p);
+  pa.offs = static_cast<uint16_t*>(ctx->pt_offs.p);
+  pa.wsum = static_cast<cpz::ge_p3*>(ctx->pt_wsum.p);
+  pa.part = static_cast<cpz::ge_p3*>(ctx->pt_part.p);
+  pa.fail = static_cast<uint8_t*>(ctx->pt_fail.p);
+  pa.blk0 = 0;
+  pa.nblk = nblk;
+  if (!timed) {  // the guard's sample, beside the bisection's MSMs: not a stage of its own
+    CPZ_HIP(cpz::launch_part_msm(pa, sc));
+    CPZ_HIP(cpz::launch_part_combine(pa, sc));
+    return CPZ_OK;
+  }
+  StageTimer t(ctx, 3, sc);
+  CPZ_HIP(cpz::launch_part_sort(pa, sc));
+  {
+    StageTimer ta(ctx, 14, sc);
+    CPZ_HIP(cpz::launch_part_acc(pa, sc));
+  }
+  CPZ_HIP(cpz::launch_part_combine(pa, sc));
+  return CPZ_OK;
+}
+
+// The dense-case guard of the bisection's partitioned branch.  Where most blocks fail (from ~0.5 %
+// invalid entries) the block pass is wasted: 11 ms beside the 80 ms of per-proof verification at
+// 2^20 entries, and even a 64-block launch costs its ~1.7 ms of latency (one wave walks a block).
+// So a range that may end in pairs_part has the partials of kPairGuardBlocks consecutive blocks
+// from its middle computed on a stream of their own while the rest of the bisection's sub-range
+// MSMs run, which hides that latency; if more than half of them fail, the range takes the
+// per-proof path.  The sample is launched when the third of the eight parts has failed: a batch
+// with few invalid entries never pays for it (launched before the first MSM it cost such a batch
+// 0.6 ms at 2^17 entries and 1.1 ms at 2^20, 3-4 %, against a parent's spread of 0.1-0.4 ms), and
+// the dense branch needs five failing parts, so at least two MSMs still run beside it.
+// The sample steers the route only: every route gives exact statuses.
+constexpr int64_t kPairGuardBlocks = 64;
+constexpr int kPairGuardAfter = 3;  // failing parts before the sample is launched
+
+int pairs_guard_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
+  const int64_t nblk = (hi - lo + cpz::kPartProofs - 1) / cpz::kPartProofs;
+  const int64_t s0 = lo + (nblk - kPairGuardBlocks) / 2 * cpz::kPartProofs;  // whole blocks, inside [lo, hi)
+  if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
+  if (!ctx->aux_stream[0]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[0], ctx->cus, ctx->device, &ctx->own_queues));
+  CPZ_HIP(hipEventRecord(ctx->aux_start, st));  // after the prepare
+  CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[0], ctx->aux_start, 0));
+  PartPairs px;
+  return pairs_part_pass(ctx, b, s0, s0 + kPairGuardBlocks * cpz::kPartProofs, ctx->aux_stream[0], px, false);
+}
+
+// Failing blocks among the sampled (waits for the sample).
+int pairs_guard_read(cpz_ctx* ctx, int* failing) {
+  uint8_t f[kPairGuardBlocks];
+  CPZ_HIP(hipMemcpyAsync(f, ctx->pt_fail.p, sizeof(f), hipMemcpyDeviceToHost, ctx->aux_stream[0]));
+  CPZ_HIP(hipStreamSynchronize(ctx->aux_stream[0]));
+  *failing = 0;
+  for (uint8_t v : f) *failing += v ? 1 : 0;
+  return CPZ_OK;
+}
+
+int pairs_part(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
+  const int64_t n = hi - lo;
+  const int64_t nblk = (n + cpz::kPartProofs - 1) / cpz::kPartProofs;
+  const int64_t blo = lo / cpz::kPartProofs;
+  PartPairs px;
+  if (int rc = pairs_part_pass(ctx, b, lo, hi, st, px, true)) return rc;
+  std::vector<uint8_t> dirty((size_t)nblk);
+  CPZ_HIP(hipMemcpyAsync(dirty.data(), ctx->pt_fail.p, (size_t)nblk, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  std::vector<uint32_t> blocks;
+  for (int64_t k = 0; k < nblk; k++)
+    if (dirty[(size_t)k]) blocks.push_back((uint32_t)k);
+  ctx->fb_stats[2] += (uint64_t)nblk;
+  ctx->fb_stats[3] += blocks.size();
+  if (blocks.empty()) return CPZ_OK;
+  if (2 * (int64_t)blocks.size() > nblk) return pairs_leaf(ctx, b, lo, hi, st);  // dense: today's path
+  if (int rc = pairs_resident(ctx, b, st)) return rc;
+  CPZ_HIP(hipMemcpyAsync(ctx->pt_blocks.p, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  std::vector<uint32_t> whole = blocks, cand;
+  if (CPZ_PART_LOCATE) {
+    int rc = part_locate(ctx, n, static_cast<const uint32_t*>(b.rows[4]) + 8 * lo, b.d_status + lo, b.seed,
+                         b.first_index + (uint64_t)lo, blocks, whole, cand, st, &px);
+    if (rc) return rc;
+  }
+  // the per-proof passes take entries and blocks of the whole batch
+  uint32_t* d_list = static_cast<uint32_t*>(ctx->pt_blocks.p) + blocks.size();
+  StageTimer span(ctx, 4, st);
+  if (!cand.empty()) {
+    ctx->fb_stats[4] += (uint64_t)cand.size();
+    std::vector<uint32_t> ge(cand.size());
+    for (size_t k = 0; k < cand.size(); k++) ge[k] = cand[k] + (uint32_t)lo;
+    CPZ_HIP(hipMemcpyAsync(d_list, ge.data(), ge.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (int rc = pairs_verify_listed(ctx, b, d_list, (int64_t)ge.size(), 1, st)) return rc;
+    std::vector<uint8_t> cst(ge.size());
+    uint8_t* d_cst = static_cast<uint8_t*>(ctx->pt_lfail.p);  // |cand| <= failing blocks bytes, spent
+    CPZ_HIP(cpz::launch_gather_status(b.d_status, d_list, (int64_t)ge.size(), d_cst, st));
+    CPZ_HIP(hipMemcpyAsync(cst.data(), d_cst, ge.size(), hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+    for (size_t k = 0; k < cand.size(); k++)
+      if (cst[k] == cpz::kStatusOk) whole.push_back(cand[k] / (uint32_t)cpz::kPartProofs);
+  }
+  if (whole.empty()) return CPZ_OK;
+  std::vector<uint32_t> gw(whole.size());
+  for (size_t k = 0; k < whole.size(); k++) {
+    gw[k] = whole[k] + (uint32_t)blo;
+    ctx->fb_stats[4] += (uint64_t)std::min<int64_t>(cpz::kPartProofs, n - (int64_t)whole[k] * cpz::kPartProofs);
+  }
+  CPZ_HIP(hipMemcpyAsync(d_list, gw.data(), gw.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (int rc = pairs_verify_listed(ctx, b, d_list, (int64_t)gw.size(), cpz::kPartProofs, st)) return rc;
+  CPZ_HIP(hipStreamSynchronize(st));  // the host lists are pageable memory read by the copies above
+  return CPZ_OK;
+}
+
 // rlc_fallback for a mixed-pair batch: the same fan-out-8 bisection aligned to kRlcPrepBlock, each
 // part's partial one more MSM over the prepared points with that part's per-pair extras.
 int pairs_fallback(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st, int depth) {
@@ -2843,6 +3073,9 @@ int pairs_fallback(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream
     c = (c / cpz::kRlcPrepBlock) * cpz::kRlcPrepBlock;
     cuts[k] = k == 0 ? lo : (k == kFanout ? hi : (c < lo ? lo : c));
   }
+  static_assert(CPZ_BATCH_PAIRS_PART_MIN >= 2 * kPairGuardBlocks * cpz::kPartProofs, "the guard's sample lies inside the range");
+  const bool guard = hi - lo >= (int64_t)CPZ_BATCH_PAIRS_PART_MIN;  // may end in pairs_part
+  bool sampled = false;
   bool failing[kFanout];
   int nfail = 0;
   for (int k = 0; k < kFanout; k++) {
@@ -2855,8 +3088,25 @@ int pairs_fallback(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream
     ctx->fb_stats[5] += 1;
     failing[k] = !ident;
     nfail += failing[k] ? 1 : 0;
+    if (guard && !sampled && nfail == kPairGuardAfter) {
+      if (int rc = pairs_guard_launch(ctx, b, lo, hi, st)) return rc;
+      sampled = true;
+    }
   }
-  if (2 * nfail > kFanout) return pairs_leaf(ctx, b, lo, hi, st);  // dense failures: no pruning left
+  static_assert(2 * kPairGuardAfter <= kFanout + 1, "the dense branch is reached only with the sample launched");
+  int sample_bad = 0;
+  if (sampled)  // also: the sample's buffers are free again before anything below reuses them
+    if (int rc = pairs_guard_read(ctx, &sample_bad)) return rc;
+  if (2 * nfail > kFanout) {  // dense failures: no pruning left
+    if (sampled) {
+      ctx->fb_stats[1] += (uint64_t)sample_bad;
+      if (2 * sample_bad <= kPairGuardBlocks) {
+        ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
+        return pairs_part(ctx, b, lo, hi, st);
+      }
+    }
+    return pairs_leaf(ctx, b, lo, hi, st);
+  }
   for (int k = 0; k < kFanout; k++) {
     if (!failing[k]) continue;
     if (int rc = pairs_fallback(ctx, b, cuts[k], cuts[k + 1], st, depth + 1)) return rc;
@@ -2980,6 +3230,8 @@ int cpz_verify_batch_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const
   b.cp = dcp;
   b.d_idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(dex) + npairs * sizeof(cpz::PairDesc));
   b.d_status = static_cast<uint8_t*>(ctx->st.p);
+  b.seed = seed;
+  b.first_index = first_index;
   {
     cpz::ChallengeArgs ca{};
     ca.eq_only = ctx->call_eq ? 1 : 0;
@@ -3017,8 +3269,14 @@ int cpz_verify_batch_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const
   CPZ_HIP(hipStreamSynchronize(st));
   const bool ident = words[0] != 0;
   if (!ident && status_out) {
-    ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
-    if ((rc = pairs_fallback(ctx, b, 0, (int64_t)n, st, 0))) return rc;
+    if (flags & CPZ_CALL_PARTITIONED) {  // the caller knows its density: no bisection
+      ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
+      rc = pairs_part(ctx, b, 0, (int64_t)n, st);
+    } else {
+      ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
+      rc = pairs_fallback(ctx, b, 0, (int64_t)n, st, 0);
+    }
+    if (rc) return rc;
     CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
     CPZ_HIP(hipStreamSynchronize(st));
   }

@@ -91,6 +91,12 @@ int cpz_ctx_set_commitment_checks(cpz_ctx *ctx, int enable);
  *                            cpz_ctx_set_commitment_checks(ctx, 0)): what verify_one does
  *                            with a Proof value (the mirrors of BatchVerifier / Verifier). */
 #define CPZ_CALL_EQUATIONS_ONLY 1u
+/*   CPZ_CALL_PARTITIONED     cpz_verify_batch_pairs_ex alone (every other entry point ignores it,
+ *                            and so does that one with npairs == 1): a failing batch with
+ *                            status_out is searched by the partitioned check at once, whatever
+ *                            its size, instead of by bisection -- for callers who know that
+ *                            their invalid entries are too many for bisection to prune. */
+#define CPZ_CALL_PARTITIONED 2u
 
 /* Thread-local description of the last error returned on this thread. */
 const char *cpz_last_error(void);
@@ -341,11 +347,22 @@ int cpz_verify_batch_device(cpz_ctx *ctx, const uint8_t g[32], const uint8_t h[3
  *                first_index values combine (cpz_combine_partials) to the unsharded P.
  *   status_out   optional (n).  Entries with a non-zero decode-level status carry zero weight and
  *                report it; when the batch fails, every status is what cpz_verify_each_pairs_ex
- *                reports for that entry.  The fallback is the bisection alone (the density probe
- *                and the partitioned check serve one pair), hence CPZ_BATCH_PAIRS_MAX_PROOFS.
+ *                reports for that entry.  The fallback is the bisection (no density probe, hence
+ *                CPZ_BATCH_PAIRS_MAX_PROOFS); a range of at least CPZ_BATCH_PAIRS_PART_MIN entries
+ *                most of whose eight parts fail -- and with CPZ_CALL_PARTITIONED the whole failing
+ *                batch -- goes to the partitioned check instead of per-proof verification: every
+ *                128-entry block's partial with the block's own per-pair sums on its pairs'
+ *                points, the failing blocks' index-weighted partials, and per-proof verification
+ *                under each entry's own pair of the located entries and of the blocks holding
+ *                more than one invalid entry.  Where more than half of the blocks fail, the
+ *                range is verified per proof after all; the automatic route first looks at the
+ *                partials of 64 blocks from the range's middle, computed beside the bisection's
+ *                MSMs, and goes straight to per-proof verification if most of those fail.  The
+ *                sample and the flag choose the route only: every route reports exact statuses.
  *   seed         secret and unpredictable, as for cpz_verify_batch.
  * CPZ_CALL_EQUATIONS_ONLY and the context's commitment-check mode apply as for cpz_verify_batch;
- * cpz_ctx_fallback_stats reports CPZ_FALLBACK_NONE or _BISECTION with out[4] and out[5].
+ * cpz_ctx_fallback_stats reports CPZ_FALLBACK_NONE, _BISECTION with out[4] and out[5], or
+ * _PARTITIONED with out[2] .. out[7] (out[5] the bisection's MSMs before it).
  * npairs == 1 is cpz_verify_batch_ex under that pair.  Checked before anything is staged,
  * cpz_last_error naming the pair or the entry, and no output buffer is written on an error:
  * n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_PAIRS_MAX, n > CPZ_BATCH_PAIRS_MAX_PROOFS, a
@@ -353,6 +370,7 @@ int cpz_verify_batch_device(cpz_ctx *ctx, const uint8_t g[32], const uint8_t h[3
  * pair that is the identity, has g == h or does not decode -> CPZ_EGENERATOR.  Host buffers
  * only: the indices are checked on the host and the kernels trust them. */
 #define CPZ_BATCH_PAIRS_MAX_PROOFS 1048576 /* 1 << 20 */
+#define CPZ_BATCH_PAIRS_PART_MIN 524288 /* 1 << 19 */
 int cpz_verify_batch_pairs(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
                            const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
                            const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
@@ -366,15 +384,17 @@ int cpz_verify_batch_pairs_ex(cpz_ctx *ctx, uint32_t flags, size_t npairs, const
                               const uint8_t *ctx_present, const uint8_t seed[32], uint64_t first_index,
                               uint8_t partial_out[32], int *batch_ok, uint8_t *status_out);
 
-/* What the last cpz_verify_batch[_device] call on the context did to locate invalid entries
- * (fallback != 0), for tests and benchmarks:
+/* What the last cpz_verify_batch[_device] or cpz_verify_batch_pairs call on the context did to
+ * locate invalid entries (fallback != 0, or status_out given), for tests and benchmarks; a
+ * mixed-pair batch that reaches the partitioned check in several ranges reports their totals:
  *   out[0]  path: CPZ_FALLBACK_NONE (the batch passed, or no fallback), _BISECTION (sub-range
  *           RLC partials, per-proof leaves: a failed batch below 2^19 proofs), _PARTITIONED
  *           (every 128-proof block's partial, the failing blocks' index-weighted partials,
  *           per-proof verification of the located entries and of the blocks not located: the
  *           density probe's moderate densities, and a failed batch of 2^19 proofs or more),
  *           _PER_PROOF (dense: everything)
- *   out[1]  invalid entries the density probe saw (0 without a probe)
+ *   out[1]  invalid entries the density probe saw (0 without a probe); cpz_verify_batch_pairs:
+ *           failing blocks among the 64 sampled ahead of the partitioned check
  *   out[2]  blocks whose partial the partitioned check computed
  *   out[3]  blocks whose partial was not the identity
  *   out[4]  entries the fallback verified per proof

@@ -48,9 +48,11 @@ pub const CPZ_PARSE_ZERO_S: u8 = 20;
 pub const CPZ_NUM_STAGES: usize = 16;
 pub const CPZ_ABI_VERSION: c_int = 5;
 pub const CPZ_CALL_EQUATIONS_ONLY: u32 = 1;
+pub const CPZ_CALL_PARTITIONED: u32 = 2;
 pub const CPZ_PAIRS_MAX: usize = 64;
 pub const CPZ_PAIRS_MAX_PROOFS: usize = 2048;
 pub const CPZ_BATCH_PAIRS_MAX_PROOFS: usize = 1048576;
+pub const CPZ_BATCH_PAIRS_PART_MIN: usize = 524288;
 pub const CPZ_PAIRS_BULK_MAX_PROOFS: usize = 1048576;
 pub const CPZ_PROVE_PAIRS_MAX_PROOFS: usize = 1048576;
 pub const CPZ_FALLBACK_STATS: usize = 8;
