@@ -285,6 +285,17 @@ def _pair_indices(pair_idx, n: int, npairs: int) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
+def _pair_rows(pairs) -> np.ndarray:
+    """The rows of Gpu.load_pairs / pairs_resident (64 bytes per pair, g then h): a sequence of
+    Parameters (1 .. PAIRS_MAX of them: the library's check), anything else is InvalidParams."""
+    if isinstance(pairs, (Parameters, bytes, bytearray, str)) or not hasattr(pairs, "__len__"):
+        raise InvalidParams("pairs must be a sequence of Parameters, not %s" % type(pairs).__name__)
+    for k, p in enumerate(pairs):
+        if not isinstance(p, Parameters):
+            raise InvalidParams("pairs[%d] is %s, not Parameters" % (k, type(p).__name__))
+    return np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+
+
 def _pair_index_tensor(pair_idx, n: int) -> None:
     """pair_idx of the device forms: a contiguous int32 or uint32 device tensor of n elements (its
     values are checked by the library, on the device)."""
@@ -497,6 +508,26 @@ class Gpu:
             self._h, npairs, _ptr(gh), n, _ptr(idx), _ptr(xs), _ptr(ks), _ptr(blob), _ptr(off), _ptr(present),
             *[_ptr(outs[q]) for q in ("y1", "y2", "r1", "r2", "s")]))
         return outs
+
+    def load_pairs(self, pairs: Sequence[Parameters]) -> int:
+        """Make every pair's 128-entry tables resident in one pass (cpz_ctx_load_pairs), as the
+        mixed-pair calls do for their own pairs: a context warmed before its first request.
+        pairs: 1 .. PAIRS_MAX Parameters (their type is checked here before the library is called,
+        their number by the library); rows may repeat.
+        Returns the number of table sets built (0: all were resident)."""
+        gh = _pair_rows(pairs)
+        built = ctypes.c_size_t(0)
+        _native.check(self._lib.cpz_ctx_load_pairs(self._h, len(pairs), _ptr(gh), ctypes.byref(built)))
+        return int(built.value)
+
+    def pairs_resident(self, pairs: Sequence[Parameters]) -> np.ndarray:
+        """bool[len(pairs)]: whether each pair has cached tables, full or light, so that a
+        mixed-pair call builds nothing for it (cpz_ctx_pairs_resident).  Builds nothing and
+        leaves the cache and its least-recently-used order as they are."""
+        gh = _pair_rows(pairs)
+        out = np.zeros(len(pairs), dtype=np.uint8)
+        _native.check(self._lib.cpz_ctx_pairs_resident(self._h, len(pairs), _ptr(gh), _ptr(out)))
+        return out.astype(bool)
 
     def decode_points(self, points):
         """Bulk element_from_bytes + element_to_bytes (cpz_decode_points): (ok uint8[n],

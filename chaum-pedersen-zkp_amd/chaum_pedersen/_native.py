@@ -37,7 +37,7 @@ EXPORTED = (
     "cpz_verify_each_ex", "cpz_verify_batch_ex", "cpz_verify_response_ex",
     "cpz_verify_each_pairs", "cpz_verify_each_pairs_ex", "cpz_verify_batch_pairs", "cpz_verify_batch_pairs_ex",
     "cpz_verify_each_pairs_bulk", "cpz_verify_each_pairs_bulk_ex", "cpz_verify_each_pairs_device",
-    "cpz_prove_pairs", "cpz_prove_pairs_device",
+    "cpz_prove_pairs", "cpz_prove_pairs_device", "cpz_ctx_load_pairs", "cpz_ctx_pairs_resident",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
@@ -149,6 +149,10 @@ def _declare(lib):
     lib.cpz_prove_pairs_device.restype = ctypes.c_int
     lib.cpz_prove_pairs_device.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p, _p, _p, _p, _p] +
                                            [_p] * 5 + [_p])
+    lib.cpz_ctx_load_pairs.restype = ctypes.c_int
+    lib.cpz_ctx_load_pairs.argtypes = [_p, ctypes.c_size_t, _p, ctypes.POINTER(ctypes.c_size_t)]
+    lib.cpz_ctx_pairs_resident.restype = ctypes.c_int
+    lib.cpz_ctx_pairs_resident.argtypes = [_p, ctypes.c_size_t, _p, _p]
     lib.cpz_decode_points.restype = ctypes.c_int
     lib.cpz_decode_points.argtypes = [_p, ctypes.c_size_t, _p, _p, _p]
     lib.cpz_abi_version.restype = ctypes.c_int

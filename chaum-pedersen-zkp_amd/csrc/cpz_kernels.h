@@ -238,6 +238,19 @@ hipError_t launch_build_niels(const uint32_t* base_words, int nbases, ge_niels* 
                               hipStream_t st);
 // The Niels tables' fields as canonical 16-bit limbs (VerifyArgs::vtab16): n entries.
 hipError_t launch_niels_r16(const ge_niels* tab, int32_t* out, int n, hipStream_t st);
+// The light sets of npairs >= 1 pairs in one pass of two launches: for pair p (encodings at
+// gh_words[16 p ..]) what launch_build_niels with two bases, launch_niels_r16 and
+// launch_transcript_prefix leave for one pair, byte for byte, into dst[p]'s buffers; out[p]
+// receives the decode flags and a copy of the snapshots for the host.  `bases` is scratch for
+// 2 * kNielsLevels ge_p3 per pair.  dst, gh_words, bases and out are device arrays of npairs rows.
+struct PairSetDst {
+  ge_niels* tab;                 // GenSet::tab: 2 * kNielsLevels * kNielsEntries entries
+  int32_t* tab16;                // GenSet::tab16: 48 limbs per entry
+  StrobeSnap* prefix;            // GenSet::prefix: 2 snapshots
+  uint32_t* gh_words;            // GenSet::gh_words: 16 words
+};
+hipError_t launch_build_pair_sets(const PairSetDst* dst, const uint32_t* gh_words, int npairs, ge_p3* bases,
+                                  PairSetup* out, hipStream_t st);
 hipError_t launch_parse_proofs(const ParseArgs& a, hipStream_t st);
 // Fixed-base combs of 2 bases (g, h): bases_scratch holds 2 * kCombWindows ge_p3.
 hipError_t launch_build_comb(const uint32_t* gh_words, ge_p3* bases_scratch, ge_niels* comb, hipStream_t st);

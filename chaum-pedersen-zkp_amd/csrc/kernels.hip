@@ -10,6 +10,8 @@
 //   k_challenge_noctx    the same for batches without contexts (registers only)
 //   k_niels_bases /      (k * B) for k = 1..128, B in {g, h} x {2^(32 m): m = 0..7}: affine
 //   k_build_niels        Niels tables
+//   k_pair_sets_bases /  the same tables, their 16-bit-limb rows and the transcript snapshots of k >= 1
+//   k_pair_sets_entries  pairs in one pass, each pair's into its own set's buffers
 //   k_verify_each        1 thread / proof: challenge split v c = u (mod l) with
 //                        u, |v| < 2^127 (verify.h), 4 ristretto decodes, then per equation
 //                        [v s] B - [u] y - [v] r in E[4]  <=>  [s] B - [c] y == r
@@ -212,10 +214,9 @@ __global__ void __launch_bounds__(256) k_challenge_noctx(ChallengeArgs a) {
 // k_build_niels: one thread per entry, [k] B_b by
 // double-and-add and one inversion to affine Niels.  A variable-base call's cold (g, h) waits
 // for both (ensure_generators).
-__global__ void __launch_bounds__(64) k_niels_bases(const uint32_t* __restrict__ base_words, int nbases,
-                                                     ge_p3* __restrict__ bases, int* __restrict__ ok) {
-  const int b = threadIdx.x >> 2, q = threadIdx.x & 3;
-  if (b >= kNielsLevels * nbases) return;  // whole quads
+// One lane of quad b's work in k_niels_bases (every lane of the quad calls it).
+__device__ __forceinline__ void niels_base_quad(const uint32_t* __restrict__ base_words, int nbases, int b, int q,
+                                                ge_p3* __restrict__ bases, int* __restrict__ ok) {
   ge_p3 B;
   const bool dec = ristretto_decode(B, base_words + 8 * (b % nbases));
   if (b < nbases && q == 0) ok[b] = dec ? 1 : 0;
@@ -224,13 +225,23 @@ __global__ void __launch_bounds__(64) k_niels_bases(const uint32_t* __restrict__
   if (q == 0) bases[b] = B;
 }
 
+// Entry t of k_build_niels' tables: [t % kNielsEntries + 1] bases[t / kNielsEntries].
+__device__ __forceinline__ ge_niels niels_entry(const ge_p3* __restrict__ bases, int t) {
+  return p3_to_niels(small_mul(bases[t / kNielsEntries], t % kNielsEntries + 1));
+}
+
+__global__ void __launch_bounds__(64) k_niels_bases(const uint32_t* __restrict__ base_words, int nbases,
+                                                     ge_p3* __restrict__ bases, int* __restrict__ ok) {
+  const int b = threadIdx.x >> 2, q = threadIdx.x & 3;
+  if (b >= kNielsLevels * nbases) return;  // whole quads
+  niels_base_quad(base_words, nbases, b, q, bases, ok);
+}
+
 __global__ void __launch_bounds__(64) k_build_niels(const ge_p3* __restrict__ bases, int nbases,
                                                     ge_niels* __restrict__ tab) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= kNielsLevels * nbases * kNielsEntries) return;
-  const int b = t / kNielsEntries;
-  const int k = t % kNielsEntries + 1;
-  tab[t] = p3_to_niels(small_mul(bases[b], k));
+  tab[t] = niels_entry(bases, t);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -661,20 +672,91 @@ hipError_t launch_build_niels(const uint32_t* base_words, int nbases, ge_niels* 
   return hipGetLastError();
 }
 
-__global__ void k_niels_r16(const ge_niels* __restrict__ tab, int32_t* __restrict__ out, int n) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;  // entry * 3 + field
-  if (t >= 3 * n) return;
-  const ge_niels& e = tab[t / 3];
-  const int f = t % 3;
+// Field f (Y+X, Y-X, 2dxy) of a Niels entry as 16 canonical 16-bit limbs (k_niels_r16's row).
+__device__ __forceinline__ void niels_r16_row(const ge_niels& e, int f, int32_t* __restrict__ out) {
   uint32_t w[8];
   fe_towords(w, f == 0 ? e.ypx : (f == 1 ? e.ymx : e.xy2d));
 #pragma unroll
-  for (int k = 0; k < 16; k++) out[16 * t + k] = (int32_t)((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+  for (int k = 0; k < 16; k++) out[k] = (int32_t)((w[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+}
+
+__global__ void k_niels_r16(const ge_niels* __restrict__ tab, int32_t* __restrict__ out, int n) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;  // entry * 3 + field
+  if (t >= 3 * n) return;
+  niels_r16_row(tab[t / 3], t % 3, out + 16 * t);
 }
 
 hipError_t launch_niels_r16(const ge_niels* tab, int32_t* out, int n, hipStream_t st) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_niels_r16, dim3((3 * n + 255) / 256), dim3(256), 0, st, tab, out, n);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// The light sets of k >= 1 pairs in one pass (the runtime's load_pairs): what launch_build_niels
+// (two bases), launch_niels_r16 and launch_transcript_prefix leave for one pair, for every pair
+// of the list at once, each into its own set's buffers (PairSetDst).  Two launches.
+// k_pair_sets_bases: workgroup p serves pair p.  Wave 0 is k_niels_bases' wave -- 16 quads, the
+// pair's 16 level bases into bases[16 p ..], the decode flags into out[p].ok -- and wave 1's
+// first lane takes the transcript snapshots as k_pair_setup's wave 0 does, into the set's prefix
+// and into out[p] (the host's copy, read back for all pairs at once); it also leaves the
+// encodings in the set's gh_words.
+// k_pair_sets_entries: one thread per Niels entry (blockIdx.y the pair), k_build_niels' entry
+// into the set's tab and, from the same registers, k_niels_r16's three rows into its tab16.
+// ---------------------------------------------------------------------------------------
+constexpr int kSetBases = 2 * kNielsLevels;            // g and h at every level
+constexpr int kSetEntries = kSetBases * kNielsEntries;  // 2048
+static_assert(kSetBases * 4 == 64, "a pair's bases are one wave of quads");
+static_assert(kSetEntries % 64 == 0, "whole waves of entries per pair");
+
+__global__ void __launch_bounds__(128) k_pair_sets_bases(const PairSetDst* __restrict__ dst,
+                                                         const uint32_t* __restrict__ gh_words,
+                                                         ge_p3* __restrict__ bases, PairSetup* __restrict__ out) {
+  __shared__ uint32_t sponge[50];
+  const int p = blockIdx.x;
+  const uint32_t* gh = gh_words + 16 * p;
+  if (threadIdx.x < 64) {
+    niels_base_quad(gh, 2, threadIdx.x >> 2, threadIdx.x & 3, bases + kSetBases * p, out[p].ok);
+    return;
+  }
+  if (threadIdx.x != 64) return;
+  const PairSetDst d = dst[p];
+  for (int k = 0; k < 16; k++) d.gh_words[k] = gh[k];
+  LdsState st{sponge, 0, 1};
+  Strobe<LdsState> s = transcript_new(st);
+  for (int j = 0; j < 2; j++) {
+    if (j == 1) transcript_parameters(s, gh, gh + 8);
+    uint32_t* own = reinterpret_cast<uint32_t*>(d.prefix[j].state);
+    uint32_t* back = reinterpret_cast<uint32_t*>(out[p].prefix[j].state);
+    for (int k = 0; k < 50; k++) own[k] = back[k] = sponge[k];
+    d.prefix[j].pos = out[p].prefix[j].pos = s.pos;
+    d.prefix[j].pos_begin = out[p].prefix[j].pos_begin = s.pos_begin;
+    d.prefix[j].flags = out[p].prefix[j].flags = s.cur_flags;
+    d.prefix[j].pad = out[p].prefix[j].pad = 0;
+  }
+}
+
+__global__ void __launch_bounds__(64) k_pair_sets_entries(const PairSetDst* __restrict__ dst,
+                                                          const ge_p3* __restrict__ bases) {
+  const int p = blockIdx.y;
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= kSetEntries) return;
+  const PairSetDst d = dst[p];
+  const ge_niels e = niels_entry(bases + kSetBases * p, t);
+  d.tab[t] = e;
+#pragma unroll 1
+  for (int f = 0; f < 3; f++) niels_r16_row(e, f, d.tab16 + 16 * (3 * t + f));
+}
+
+hipError_t launch_build_pair_sets(const PairSetDst* dst, const uint32_t* gh_words, int npairs, ge_p3* bases,
+                                  PairSetup* out, hipStream_t st) {
+  if (npairs <= 0) return hipSuccess;
+  if (npairs > 65535) return hipErrorInvalidValue;  // blockIdx.y
+  hipLaunchKernelGGL(k_pair_sets_bases, dim3((unsigned)npairs), dim3(128), 0, st, dst, gh_words, bases, out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pair_sets_entries, dim3(kSetEntries / 64, (unsigned)npairs), dim3(64), 0, st, dst,
+                     (const ge_p3*)bases);
   return hipGetLastError();
 }
 

@@ -263,6 +263,8 @@ struct cpz_ctx {
   DevBuf bp_gh, bp_setup, bp_pts, bp_desc;
   DevBuf bp_word;  // cpz_verify_each_pairs_device: the index check's word (k_pair_idx_check)
   DevBuf pp_idx;   // cpz_prove_pairs: the call's pair indices (its descriptors go to bp_desc)
+  // load_pairs, one block: the pass's destinations and encodings, its level bases, what comes back
+  DevBuf lp;
   // partitioned batch check (part.hip): sorted lists / offsets / window sums of one chunk of
   // blocks, every block's partial and fail flag, the sum's scratch, the failing-block list
   DevBuf pt_lists, pt_offs, pt_wsum, pt_part, pt_fail, pt_tmp, pt_blocks, pt_assign;
@@ -289,7 +291,7 @@ struct cpz_ctx {
 #endif
   // optional per-kernel timing
   bool timing = false;
-  struct Mark { int stage; hipEvent_t a, b; };
+  struct Mark { int stage; hipEvent_t a, b; int count = 1; };  // count: what the span adds to the stage's launch count
   std::vector<Mark> marks;
   std::vector<hipEvent_t> free_events;
 };
@@ -338,6 +340,7 @@ struct StageTimer {
   int stage;
   hipStream_t st;
   hipEvent_t a = nullptr, b = nullptr;
+  int count = 1;  // one span standing for several units of work (load_pairs: the sets it builds)
   StageTimer(cpz_ctx* c, int s, hipStream_t stream) : ctx(c), stage(s), st(stream) {
     if (ctx->timing) {
       a = take_event(ctx);
@@ -348,7 +351,7 @@ struct StageTimer {
   ~StageTimer() {
     if (a && b) {
       (void)hipEventRecord(b, st);
-      ctx->marks.push_back({stage, a, b});
+      ctx->marks.push_back({stage, a, b, count});
     }
   }
 };
@@ -1007,7 +1010,7 @@ int rlc_range_launch(cpz_ctx* ctx, int64_t lo, int64_t hi, hipStream_t st) {
                                 static_cast<const cpz::ge_niels*>(ctx->gs->tab.p), ss, timed ? marks : nullptr,
                                 fwait, fdone));
     if (timed)
-      for (int k = 0; k + 1 < cpz::kRlcMsmMarks; k++) ctx->marks.push_back({8 + k, marks[k], marks[k + 1]});
+      for (int k = 0; k + 1 < cpz::kRlcMsmMarks; k++) ctx->marks.push_back({8 + k, marks[k], marks[k + 1], 1});
   }
   return CPZ_OK;
 }
@@ -2100,7 +2103,7 @@ int cpz_ctx_stage_times_n(cpz_ctx* ctx, int nstages, double* ms_out, int* launch
     CPZ_HIP(hipEventElapsedTime(&ms, m.a, m.b));
     if (m.stage >= 0 && m.stage < nstages) {
       ms_out[m.stage] += ms;
-      if (launches_out) launches_out[m.stage] += 1;
+      if (launches_out) launches_out[m.stage] += m.count;
     }
     done.push_back(m.a);
     done.push_back(m.b);
@@ -2128,6 +2131,8 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
   }
   if (ctx->last_done) (void)hipEventDestroy(ctx->last_done);
   for (GenSet& e : ctx->gen) e.release();
+  for (GenSet& e : ctx->light) e.release();
+  for (DevBuf* b : {&ctx->lp, &ctx->gen_bases}) b->release();
   ctx->ok_flags.release();
   ctx->c.release();
   ctx->st.release();
@@ -2462,15 +2467,173 @@ int pairs_bulk_generator_checks(cpz_ctx* ctx, uint32_t flags, size_t npairs, con
   return CPZ_OK;
 }
 
+// The resident set of (g, h), full sets first as ensure_generators looks them up; null if none.
+GenSet* find_resident(cpz_ctx* ctx, const uint8_t both[64]) {
+  for (int k = 0; k < ctx->gen_cap; k++)
+    if (ctx->gen[k].valid && std::memcmp(ctx->gen[k].gh, both, 64) == 0) return &ctx->gen[k];
+  for (GenSet& e : ctx->light)
+    if (e.valid && std::memcmp(e.gh, both, 64) == 0) return &e;
+  return nullptr;
+}
+
+// CPZ_PAIRS_BUILD_BATCH=0 in the environment, read at every call: a call's missing light sets are
+// built one by one (ensure_generators per pair) instead of in load_pairs' single pass -- for
+// measurement (tools/load_pairs_ab.py) and for the equality test.
+bool pairs_build_batch() {
+  const char* v = std::getenv("CPZ_PAIRS_BUILD_BATCH");
+  return !(v && v[0] == '0');
+}
+
+// Make the npairs <= CPZ_PAIRS_MAX pairs of a list resident (the context locked, its device
+// current): a pair with a cached set, full or light, keeps it, and the light sets of all the
+// others are built in one pass -- launch_build_pair_sets, one copy back of every pair's flags and
+// snapshots, one synchronisation -- timed as one stage-13 span that counts the sets it builds.
+// Parameters::with_generators (gadgets.rs:77-103) first, per pair without a set, in
+// ensure_generators' order and wording, cpz_last_error naming the lowest offending pair: nothing
+// is launched and no set is invalidated for a list that fails (`decoded`: the caller has
+// decoded the missing pairs' encodings on the host already, pairs_bulk_generator_checks).
+// The call's own resident sets are stamped before any victim is chosen, so none of them is
+// evicted; repeated rows are built once.  ctx->gs ends on the last pair's set.  desc (optional):
+// every pair's descriptor row.  built (optional): the sets built.
+int load_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, cpz::PairDesc* desc, bool decoded, size_t* built) {
+  static_assert(CPZ_PAIRS_MAX <= kLightCache, "every pair of a call is resident at once");
+  if (built) *built = 0;
+  if (npairs == 0 || npairs > CPZ_PAIRS_MAX) return fail(CPZ_EINVAL, "internal: load_pairs outside 1 .. CPZ_PAIRS_MAX");
+  if (!pairs_build_batch()) {
+    for (size_t p = 0; p < npairs; p++) {
+      const bool had = pair_resident(ctx, pairs + 64 * p);
+      int rc = ensure_generators(ctx, pairs + 64 * p, pairs + 64 * p + 32, false, true);
+      if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
+      if (built && !had) *built += 1;
+      if (desc) pair_desc(desc[p], *ctx->gs);
+    }
+    return CPZ_OK;
+  }
+  // the checks, for every row without a set
+  static const uint8_t zero[32] = {0};
+  GenSet* set[CPZ_PAIRS_MAX];
+  for (size_t p = 0; p < npairs; p++) {
+    const uint8_t *g = pairs + 64 * p, *h = g + 32;
+    if ((set[p] = find_resident(ctx, g))) continue;
+    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
+    if (std::memcmp(g, h, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
+    if (decoded) continue;
+    uint32_t w[16];
+    std::memcpy(w, g, 64);
+    cpz::ge_p3 pt;
+    if (!cpz::ristretto_decode(pt, w) || !cpz::ristretto_decode(pt, w + 8))
+      return fail(CPZ_EGENERATOR,
+                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
+  }
+  // the call's resident sets stamped, the missing rows deduplicated: row[j] is the first row of
+  // the j-th set to build, first[p] the index j of row p's set
+  size_t row[CPZ_PAIRS_MAX], nbuild = 0;
+  int first[CPZ_PAIRS_MAX];
+  for (size_t p = 0; p < npairs; p++) {
+    first[p] = -1;
+    if (set[p]) {
+      set[p]->used = ++ctx->gen_clock;
+      continue;
+    }
+    for (size_t j = 0; j < nbuild && first[p] < 0; j++)
+      if (std::memcmp(pairs + 64 * row[j], pairs + 64 * p, 64) == 0) first[p] = (int)j;
+    if (first[p] < 0) {
+      first[p] = (int)nbuild;
+      row[nbuild++] = p;
+    }
+  }
+  if (nbuild) {
+    // Victims: the least recently used light sets (unused ones first) that this call neither
+    // reads nor has taken already.  They are about to be overwritten: no earlier call's kernels
+    // may still be reading them.
+    if (ctx->have_last) CPZ_HIP(hipEventSynchronize(ctx->last_done));
+    bool held[kLightCache] = {};
+    for (size_t p = 0; p < npairs; p++)
+      if (set[p] && !set[p]->full) held[set[p] - ctx->light] = true;
+    GenSet* victim[CPZ_PAIRS_MAX];
+    for (size_t j = 0; j < nbuild; j++) {
+      int v = -1;
+      for (int k = 0; k < kLightCache; k++) {
+        if (held[k]) continue;
+        const GenSet &e = ctx->light[k], *b = v < 0 ? nullptr : &ctx->light[v];
+        if (!b || (!e.valid && b->valid) || (e.valid == b->valid && e.used < b->used)) v = k;
+      }
+      if (v < 0) return fail(CPZ_EHIP, "internal: no light set left for a call's pairs");
+      held[v] = true;
+      victim[j] = &ctx->light[v];
+    }
+    std::vector<uint8_t> in(nbuild * (sizeof(cpz::PairSetDst) + 64));
+    for (size_t j = 0; j < nbuild; j++) {
+      GenSet& e = *victim[j];
+      e.valid = false;
+      e.full = false;
+      if (ctx->gs == &e) ctx->gs = nullptr;
+      CPZ_HIP(e.tab.ensure(2 * cpz::kNielsLevels * cpz::kNielsEntries * sizeof(cpz::ge_niels)));
+      CPZ_HIP(e.tab16.ensure(2 * cpz::kNielsLevels * cpz::kNielsEntries * 48 * sizeof(int32_t)));
+      CPZ_HIP(e.prefix.ensure(2 * sizeof(cpz::StrobeSnap)));
+      CPZ_HIP(e.gh_words.ensure(64));
+      cpz::PairSetDst d;
+      d.tab = static_cast<cpz::ge_niels*>(e.tab.p);
+      d.tab16 = static_cast<int32_t*>(e.tab16.p);
+      d.prefix = static_cast<cpz::StrobeSnap*>(e.prefix.p);
+      d.gh_words = static_cast<uint32_t*>(e.gh_words.p);
+      std::memcpy(in.data() + j * sizeof(d), &d, sizeof(d));
+      std::memcpy(in.data() + nbuild * sizeof(d) + 64 * j, pairs + 64 * row[j], 64);
+    }
+    // one block for the pass, sized for CPZ_PAIRS_MAX pairs: [destinations, encodings][level bases][setup rows]
+    constexpr size_t kInBytes = CPZ_PAIRS_MAX * (sizeof(cpz::PairSetDst) + 64);
+    constexpr size_t kBasesBytes = (size_t)CPZ_PAIRS_MAX * 2 * cpz::kNielsLevels * sizeof(cpz::ge_p3);
+    static_assert(kInBytes % 16 == 0 && kBasesBytes % 16 == 0, "the block's parts stay 16-byte aligned");
+    CPZ_HIP(ctx->lp.ensure(kInBytes + kBasesBytes + CPZ_PAIRS_MAX * sizeof(cpz::PairSetup)));
+    uint8_t* const d_in = static_cast<uint8_t*>(ctx->lp.p);
+    cpz::ge_p3* const d_bases = reinterpret_cast<cpz::ge_p3*>(d_in + kInBytes);
+    cpz::PairSetup* const d_setup = reinterpret_cast<cpz::PairSetup*>(d_in + kInBytes + kBasesBytes);
+    std::vector<cpz::PairSetup> setup(nbuild);
+    {
+      StageTimer timer(ctx, 13, ctx->stream);
+      timer.count = (int)nbuild;
+      CPZ_HIP(hipMemcpyAsync(d_in, in.data(), in.size(), hipMemcpyHostToDevice, ctx->stream));
+      CPZ_HIP(cpz::launch_build_pair_sets(reinterpret_cast<const cpz::PairSetDst*>(d_in),
+                                          reinterpret_cast<const uint32_t*>(d_in + nbuild * sizeof(cpz::PairSetDst)),
+                                          (int)nbuild, d_bases, d_setup, ctx->stream));
+      CPZ_HIP(hipMemcpyAsync(setup.data(), d_setup, nbuild * sizeof(cpz::PairSetup), hipMemcpyDeviceToHost,
+                             ctx->stream));
+      CPZ_HIP(hipStreamSynchronize(ctx->stream));  // callers may launch on another stream
+    }
+    // (only a pair the caller's own check saw resident and another thread's call evicted since
+    // can fail here: every other encoding was decoded on the host above or by the caller)
+    for (size_t j = 0; j < nbuild; j++)
+      if (!setup[j].ok[0] || !setup[j].ok[1])
+        return fail(CPZ_EGENERATOR, "pair " + std::to_string(row[j]) +
+                                        ": generator encoding does not decode to a ristretto255 point");
+    for (size_t j = 0; j < nbuild; j++) {
+      GenSet& e = *victim[j];
+      const uint8_t* both = pairs + 64 * row[j];
+      std::memcpy(e.snap, setup[j].prefix, sizeof(e.snap));
+      e.prefix_fixed = cpz::challenge_prefix_is_fixed(e.snap[1]) && cpz::challenge_masks(e.chal_k1, e.chal_k2);
+      uint32_t gw[16];
+      std::memcpy(gw, both, 64);
+      e.ctx32_fixed = cpz::challenge_prefix_is_ctx32(e.snap[0]) && cpz::challenge_masks_ctx32(e.chal_c32, gw, gw + 8);
+      std::memcpy(e.gh, both, 64);
+      e.valid = true;
+      e.used = ++ctx->gen_clock;
+    }
+    for (size_t p = 0; p < npairs; p++)
+      if (!set[p]) set[p] = victim[first[p]];
+    if (built) *built = nbuild;
+  }
+  ctx->gs = set[npairs - 1];
+  if (desc)
+    for (size_t p = 0; p < npairs; p++) pair_desc(desc[p], *set[p]);
+  return CPZ_OK;
+}
+
 // Every pair of the call resident (light sets at stage 13 unless a full one is cached; no combs)
 // and its descriptor row written to desc[p].
 int pairs_make_resident(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, cpz::PairDesc* desc) {
-  for (size_t p = 0; p < npairs; p++) {
-    int rc = ensure_generators(ctx, pairs + 64 * p, pairs + 64 * p + 32, false, true);
-    if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
-    pair_desc(desc[p], *ctx->gs);
-  }
-  return CPZ_OK;
+  return load_pairs(ctx, npairs, pairs, desc, true, nullptr);
 }
 
 }  // namespace
@@ -2518,20 +2681,16 @@ int cpz_verify_each_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const 
                               status_out);
   CallLock lock(ctx, flags);
   CPZ_HIP(hipSetDevice(ctx->device));
-  // Every pair's set, full or light, resident at once: each is stamped as it is resolved, so
-  // with at most kLightCache pairs the least recently used light set is never this call's.
-  // The descriptor table and the indices go to the device in one block (stage_inputs' extra).
-  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
-  for (size_t p = 0; p < npairs; p++) {
-    int rc = ensure_generators(ctx, pairs + 64 * p, pairs + 64 * p + 32, false, true);
-    if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
-    cpz::PairDesc d;
-    pair_desc(d, *ctx->gs);
-    std::memcpy(extra.data() + p * sizeof(cpz::PairDesc), &d, sizeof(d));
-  }
-  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
-  int rc = order_after_last(ctx, ctx->stream);
+  // Every pair's set, full or light, resident at once (load_pairs: the missing ones built in one
+  // pass, the encodings decoded on the host first).  The descriptor table and the indices go to
+  // the device in one block (stage_inputs' extra).
+  std::vector<cpz::PairDesc> desc(npairs);
+  int rc = load_pairs(ctx, npairs, pairs, desc.data(), false, nullptr);
   if (rc) return rc;
+  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
+  std::memcpy(extra.data(), desc.data(), npairs * sizeof(cpz::PairDesc));
+  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  if ((rc = order_after_last(ctx, ctx->stream))) return rc;
   const uint8_t* host[5] = {y1, y2, r1, r2, s};
   const void* dev[5];
   const void* dcb;
@@ -2738,6 +2897,31 @@ int cpz_verify_each_pairs_device(cpz_ctx* ctx, uint32_t flags, size_t npairs, co
   return CPZ_OK;
 }
 
+int cpz_ctx_load_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t* built_out) {
+  if (built_out) *built_out = 0;
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
+  if (npairs > CPZ_PAIRS_MAX)
+    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
+                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (!pairs) return fail(CPZ_EINVAL, "null input pointer");
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  return load_pairs(ctx, npairs, pairs, nullptr, false, built_out);
+}
+
+int cpz_ctx_pairs_resident(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, uint8_t* resident_out) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
+  if (npairs > CPZ_PAIRS_MAX)
+    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
+                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (!pairs || !resident_out) return fail(CPZ_EINVAL, "null input pointer");
+  CallLock lock(ctx);
+  for (size_t p = 0; p < npairs; p++) resident_out[p] = pair_resident(ctx, pairs + 64 * p) ? 1 : 0;
+  return CPZ_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -2798,11 +2982,7 @@ int pairs_range_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi,
 int pairs_resident(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
   if (!b.d_full) {
     std::vector<cpz::PairDesc> full(b.npairs);
-    for (size_t p = 0; p < b.npairs; p++) {
-      int rc = ensure_generators(ctx, b.pairs + 64 * p, b.pairs + 64 * p + 32, false, true);
-      if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
-      pair_desc(full[p], *ctx->gs);
-    }
+    if (int rc = load_pairs(ctx, b.npairs, b.pairs, full.data(), true, nullptr)) return rc;
     CPZ_HIP(ctx->bp_desc.ensure(full.size() * sizeof(cpz::PairDesc)));
     CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, full.data(), full.size() * sizeof(cpz::PairDesc), hipMemcpyHostToDevice, st));
     CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `full` goes

@@ -187,6 +187,27 @@ int cpz_verify_each_pairs_device(cpz_ctx *ctx, uint32_t flags, size_t npairs, co
                                  const void *d_ctx_bytes, const uint64_t *d_ctx_off,
                                  const uint8_t *d_ctx_present, void *d_status_out, void *stream);
 
+/* The light-set cache behind the mixed-pair calls (cpz_verify_each_pairs*, cpz_prove_pairs*, the
+ * fallback of cpz_verify_batch_pairs): a context keeps the 128-entry tables and transcript
+ * prefixes of its CPZ_PAIRS_MAX most recently used pairs, and a call finds which of its pairs
+ * have none and builds them all in ONE pass (two launches, one copy back, one synchronisation
+ * for any number of pairs: stage 13, counted per set), evicting the least recently used sets
+ * that the call itself does not read.  CPZ_PAIRS_BUILD_BATCH=0 in the environment, read at every
+ * call, restores one build per pair (for measurement).
+ *   cpz_ctx_load_pairs makes the npairs rows of `pairs` (64 bytes each, g then h; rows may
+ * repeat and may be the default pair) resident without verifying anything: a service warms a
+ * context before its first request, or before a call under another set of tenants.  A pair
+ * with cached tables, full or light, keeps them and is marked most recently used.  *built_out
+ * (optional) receives the number of sets built.  npairs == 0, npairs > CPZ_PAIRS_MAX or a null
+ * ctx / pairs -> CPZ_EINVAL; a pair without cached tables that is the identity, has g == h or
+ * does not decode -> CPZ_EGENERATOR, cpz_last_error naming the lowest such pair ("pair P: ..."),
+ * with nothing launched and no cached set touched.
+ *   cpz_ctx_pairs_resident writes resident_out[p] = 1 if row p has cached tables (full or
+ * light: a mixed-pair call would build nothing for it), else 0.  It builds nothing and changes
+ * neither the cache nor its least-recently-used order.  Same CPZ_EINVAL cases. */
+int cpz_ctx_load_pairs(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t *built_out);
+int cpz_ctx_pairs_resident(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, uint8_t *resident_out);
+
 /* cpz_verify_each with device-resident, 16-byte aligned inputs/outputs, enqueued on `stream`
  * (a hipStream_t, or NULL for the context's own stream, which is a blocking stream and so
  * is ordered with the legacy default stream).  Does not synchronise.  Any later call on the
@@ -498,7 +519,9 @@ int cpz_verify_batch_multi(cpz_ctx *const *ctxs, int nctx, const uint8_t g[32], 
  * (segment + window), 12 = window combine + encode (k_rlc_final16); 13 = variable-base generator
  * tables (a per-proof call of at most 16384 proofs on a pair other than the default one and
  * without combs in the cache builds only the pair's Niels tables and transcript prefix, ~0.5 ms
- * instead of ~3 ms, and verifies [s'] g, [s'] h from them; a context keeps 64 such pairs);
+ * instead of ~3 ms, and verifies [s'] g, [s'] h from them; a context keeps 64 such pairs; a
+ * mixed-pair call or cpz_ctx_load_pairs builds all of its missing pairs' tables in one pass,
+ * recorded as one span whose launch count is the number of sets built);
  * phases of the partitioned check (inside stage 3): 14 = every block's bucket walk
  * (k_part_acc), 15 = the locate pass's walk over the failing blocks.
  * cpz_ctx_stage_times synchronises, writes the summed milliseconds and launch counts per stage

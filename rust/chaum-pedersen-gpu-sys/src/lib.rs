@@ -146,6 +146,8 @@ extern "C" {
                                   d_ctx_bytes: *const c_void, d_ctx_off: *const u64, d_ctx_present: *const u8,
                                   d_y1: *mut c_void, d_y2: *mut c_void, d_r1: *mut c_void, d_r2: *mut c_void,
                                   d_s: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn cpz_ctx_load_pairs(ctx: *mut cpz_ctx, npairs: usize, pairs: *const u8, built_out: *mut usize) -> c_int;
+    pub fn cpz_ctx_pairs_resident(ctx: *mut cpz_ctx, npairs: usize, pairs: *const u8, resident_out: *mut u8) -> c_int;
     pub fn cpz_prove_synthetic(ctx: *mut cpz_ctx, g: *const u8, h: *const u8, n: usize, first_index: u64,
                                seed_x: *const u8, seed_k: *const u8, ctx_bytes: *const u8, ctx_off: *const u64,
                                ctx_present: *const u8, y1: *mut u8, y2: *mut u8, r1: *mut u8, r2: *mut u8,

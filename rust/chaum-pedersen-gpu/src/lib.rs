@@ -276,6 +276,35 @@ impl Gpu {
         Ok(st)
     }
 
+    /// Make the pairs' 128-entry tables resident in one pass (`cpz_ctx_load_pairs`), as the
+    /// mixed-pair calls do for their own pairs: a context warmed before its first request.  At most
+    /// `CPZ_PAIRS_MAX` pairs; rows may repeat.  Returns the number of table sets built.
+    pub fn load_pairs(&self, pairs: &[(Bytes32, Bytes32)]) -> Result<usize, GpuError> {
+        let mut gh = Vec::with_capacity(64 * pairs.len());
+        for (g, h) in pairs {
+            gh.extend_from_slice(g);
+            gh.extend_from_slice(h);
+        }
+        let mut built = 0usize;
+        // SAFETY: gh holds 64 * pairs.len() bytes; built is a local.
+        check(unsafe { sys::cpz_ctx_load_pairs(self.ctx, pairs.len(), gh.as_ptr(), &mut built) })?;
+        Ok(built)
+    }
+
+    /// Whether each pair has cached tables, so that a mixed-pair call builds nothing for it
+    /// (`cpz_ctx_pairs_resident`).  Builds nothing and leaves the cache as it is.
+    pub fn pairs_resident(&self, pairs: &[(Bytes32, Bytes32)]) -> Result<Vec<bool>, GpuError> {
+        let mut gh = Vec::with_capacity(64 * pairs.len());
+        for (g, h) in pairs {
+            gh.extend_from_slice(g);
+            gh.extend_from_slice(h);
+        }
+        let mut out = vec![0u8; pairs.len()];
+        // SAFETY: gh holds 64 * pairs.len() bytes, out pairs.len() bytes.
+        check(unsafe { sys::cpz_ctx_pairs_resident(self.ctx, pairs.len(), gh.as_ptr(), out.as_mut_ptr()) })?;
+        Ok(out.into_iter().map(|b| b != 0).collect())
+    }
+
     /// The batch check over entries that carry their own generators, in one MSM
     /// (`cpz_verify_batch_pairs_ex`): entry i stands under `pairs[pair_idx[i]]`, at most
     /// `CPZ_PAIRS_MAX` pairs and `CPZ_BATCH_PAIRS_MAX_PROOFS` entries.  Returns (partial encoding,
