@@ -17,6 +17,9 @@
                            plain C probes of the MSM's sort and reduction kernels
                            (tests/native/msmprobe.hip), for the GPU unit tests only; never linked
                            into the product.
+* ``tests/native/libcpz_pairsumprobe.so`` -- the same for rlc.hip's per-pair sum kernels
+                           (tests/native/pairsumprobe.hip), for the GPU unit tests only; never
+                           linked into the product.
 * ``oracle/``            -- delegated to oracle/Makefile (the C oracle: CPU baseline and
                            at-scale checker; test infrastructure only).
 
@@ -40,6 +43,7 @@ DEVPROBE = os.path.join(ROOT, "tests", "native", "libcpz_devprobe.so")
 PARTPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partprobe.so")
 PARTPAIRSPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partpairsprobe.so")
 MSMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_msmprobe.so")
+PAIRSUMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_pairsumprobe.so")
 ARCH = os.environ.get("CPZ_OFFLOAD_ARCH", "gfx950")
 
 
@@ -122,7 +126,7 @@ def build_hosttest(force: bool = False, out: str = HOSTTEST, defines=()) -> str:
     """`out` / `defines` build a variant of the device library elsewhere (a switch at 0), so that
     the CPU tests can hold the fallback code to the same checks."""
     srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("hostlib.cpp", "hostlib_joint.cpp", "hostlib_lean.cpp",
-                                                              "hostlib_prove.cpp")]
+                                                              "hostlib_prove.cpp", "hostlib_pairsum.cpp")]
     if not force and not _newer(out, srcs + _headers()):
         return out
     cxx = shutil.which("g++") or "g++"
@@ -186,6 +190,22 @@ def build_msmprobe(force: bool = False, out: str = MSMPROBE, include: str = CSRC
     rlc.hip itself), compiled like the product's units.  `out` / `include` build them over
     another copy of csrc (a mutated one) for tests/test_gpu_msm_probe.py's CPZ_MSMPROBE."""
     src = os.path.join(ROOT, "tests", "native", "msmprobe.hip")
+    deps = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h") or f == "rlc.hip"]
+    if not force and not _newer(out, [src] + deps):
+        return out
+    tmp = out + ".tmp"
+    _run([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", include,
+          "-I", os.path.join(ROOT, "include"), "-shared", src, "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
+def build_pairsumprobe(force: bool = False, out: str = PAIRSUMPROBE, include: str = CSRC) -> str:
+    """Probe of the per-pair sum kernels of a mixed-pair batch over many pairs
+    (tests/native/pairsumprobe.hip, which includes rlc.hip itself), compiled like the product's
+    units.  `out` / `include` build it over another copy of csrc (a mutated one) for
+    tests/test_gpu_pairsum_probe.py's CPZ_PAIRSUMPROBE."""
+    src = os.path.join(ROOT, "tests", "native", "pairsumprobe.hip")
     deps = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h") or f == "rlc.hip"]
     if not force and not _newer(out, [src] + deps):
         return out
@@ -260,6 +280,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_partprobe(force)
     build_partpairsprobe(force)
     build_msmprobe(force)
+    build_pairsumprobe(force)
     build_cpp_test(force)
     build_dropin_test(force)
     build_merge_groups_test(force)

@@ -588,6 +588,30 @@ class Gpu:
             _ptr(off), _ptr(present), bytes(seed), first_index, partial, ctypes.byref(ok), _ptr(out)))
         return partial.raw, bool(ok.value), out
 
+    def verify_batch_pairs_many(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, seed: bytes,
+                                first_index: int = 0, contexts=None, statuses: bool = True,
+                                equations_only: bool = False):
+        """verify_batch_pairs over up to BATCH_PAIRS_MANY_MAX pairs in one MSM
+        (cpz_verify_batch_pairs_many): a tenant per entry, or a bulk batch over thousands of
+        tenants.  Same arguments and the same (partial, batch_ok, status) as verify_batch_pairs;
+        up to PAIRS_MAX pairs it is that call.  Above, a passing batch builds no table; a failing
+        one with statuses=True is bisected and the ranges verified per proof build their pairs'
+        tables PAIRS_MAX at a time.  pair_idx: n integers in [0, len(pairs)), checked here before
+        the library is called."""
+        n = len(y1)
+        npairs = len(pairs)
+        idx = _pair_indices(pair_idx, n, npairs)
+        arrs = [_rows(a, n, nm) for a, nm in ((y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2"), (s, "s"))]
+        gh = np.frombuffer(b"".join(p.g + p.h for p in pairs) or b"\0", np.uint8)
+        blob, off, present = _ctx_arrays(contexts, n)
+        partial = ctypes.create_string_buffer(32)
+        ok = ctypes.c_int(0)
+        out = np.empty(n, dtype=np.uint8) if statuses else None
+        _native.check(self._lib.cpz_verify_batch_pairs_many(
+            self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
+            _ptr(off), _ptr(present), bytes(seed), first_index, partial, ctypes.byref(ok), _ptr(out)))
+        return partial.raw, bool(ok.value), out
+
     def verify_batch_device(self, y1, y2, r1, r2, s, status_out, seed: bytes, first_index: int = 0,
                             fallback: bool = False, params: Optional[Parameters] = None,
                             stream: Optional[int] = None, ctx_bytes=None, ctx_off=None, ctx_present=None):

@@ -226,6 +226,12 @@ hipError_t launch_challenge(const ChallengeArgs& a, hipStream_t st);
 // Every pair of a mixed-pair batch check in one launch (a workgroup per pair): the transcript
 // snapshots and decode flags into out[p], g_p and h_p as affine Niels points into pts[2 p ..].
 hipError_t launch_pair_setup(const uint32_t* gh_words, int npairs, PairSetup* out, ge_niels* pts, hipStream_t st);
+// launch_pair_setup with the table-less descriptor rows built on the device (more than
+// CPZ_PAIRS_MAX pairs): desc[p] is the row cpz_verify_batch_pairs_ex builds on the host from
+// PairSetup (null tables, snapshots, generator words, fast_noctx with the call's k1 / k2 --
+// challenge_masks' -- and fast_ctx32 with c32); ok[2 p], ok[2 p + 1] the decode flags of g_p, h_p.
+hipError_t launch_pair_desc(const uint32_t* gh_words, int npairs, const uint32_t k1[50], const uint32_t k2[50],
+                            bool masks, PairDesc* desc, int32_t* ok, ge_niels* pts, hipStream_t st);
 // k_challenge with a pair per proof (PairArgs; the descriptors' tables may be null): a's prefix,
 // gh_words and masks are unused.
 hipError_t launch_challenge_pairs(const ChallengeArgs& a, const PairArgs& pa, hipStream_t st);

@@ -102,6 +102,85 @@ __global__ void __launch_bounds__(64 * 3) k_pair_setup(const uint32_t* __restric
   }
 }
 
+__host__ __device__ __forceinline__ bool prefix_at_fixed(int pos, int pos_begin, int flags) {
+  return pos == kTailPrefixPos && pos_begin == kTailPrefixBegin && flags == kTailPrefixFlags;
+}
+__host__ __device__ __forceinline__ bool prefix_at_ctx32(int pos, int pos_begin, int flags) {
+  return pos == kC32PrefixPos && pos_begin == kC32PrefixBegin && flags == kC32PrefixFlags;
+}
+
+// k_pair_setup for a batch check over more than CPZ_PAIRS_MAX pairs (cpz_verify_batch_pairs_many):
+// the pair's whole table-less descriptor row is built here, with the functions the host loop of
+// cpz_verify_batch_pairs_ex calls, so only the decode flags (8 bytes per pair) go back to the host.
+// A workgroup serves kPairDescPairs pairs, a lane per pair in each of its four waves: wave 0 the
+// snapshots (every lane its own dword-interleaved image of the sponge in LDS), generator words,
+// fast_noctx and the call's k1 / k2 (pair-independent: derived once on the host), waves 1 and 2
+// the decodes of g and h, wave 3 the recording sponge of challenge_masks_ctx32 (c32, fast_ctx32).
+// k_pair_setup's shape -- a workgroup per pair, one lane per wave -- was tried first: its 256
+// registers (the decode) allow one wave per SIMD, so 4096 pairs ran in rounds and the launch took
+// 1.94 ms; with the lanes filled 4096 pairs are 256 waves, all resident at once.
+// (prefix[0] is Transcript::new()'s, the same for every pair.)
+struct PairDescConsts {
+  uint32_t k1[50];
+  uint32_t k2[50];
+  int32_t masks;                 // challenge_masks succeeded
+};
+constexpr int kPairDescPairs = 64;
+
+__global__ void __launch_bounds__(64 * 4) k_pair_desc(const uint32_t* __restrict__ gh_words, int npairs,
+                                                      PairDescConsts km, PairDesc* __restrict__ desc,
+                                                      int32_t* __restrict__ ok, ge_niels* __restrict__ pts) {
+  __shared__ uint32_t sponge[50 * kPairDescPairs];
+  __shared__ uint8_t c32_ok[kPairDescPairs];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p = blockIdx.x * kPairDescPairs + lane;
+  const bool live = p < npairs;
+  const uint32_t* gh = gh_words + 16 * (live ? p : 0);
+  PairDesc* d = desc + (live ? p : 0);  // written by live lanes only
+  bool pre_ctx32 = false;
+  if (live) {
+    if (w == 0) {
+      d->tab = nullptr;
+      d->tab16 = nullptr;
+      LdsState st{sponge, lane, kPairDescPairs};
+      Strobe<LdsState> s = transcript_new(st);
+      for (int j = 0; j < 2; j++) {
+        if (j == 1) transcript_parameters(s, gh, gh + 8);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(d->prefix[j].state);
+        for (int k = 0; k < 50; k++) dst[k] = sponge[k * kPairDescPairs + lane];
+        d->prefix[j].pos = s.pos;
+        d->prefix[j].pos_begin = s.pos_begin;
+        d->prefix[j].flags = s.cur_flags;
+        d->prefix[j].pad = 0;
+        if (j == 0) pre_ctx32 = prefix_at_ctx32(s.pos, s.pos_begin, s.cur_flags);
+      }
+      d->fast_noctx = km.masks && prefix_at_fixed(s.pos, s.pos_begin, s.cur_flags) ? 1 : 0;
+      for (int k = 0; k < 16; k++) d->gh_words[k] = gh[k];
+      for (int k = 0; k < 50; k++) {
+        d->k1[k] = km.k1[k];
+        d->k2[k] = km.k2[k];
+      }
+    } else if (w <= 2) {
+      const int e = w - 1;
+      uint32_t enc[8];
+      load_words8(enc, gh, e);
+      ge_p3 P;
+      ok[2 * p + e] = ristretto_decode(P, enc) ? 1 : 0;
+      store_niels(pts + 2 * p + e, niels_from_p3_affine(P, false));
+    } else {
+      uint32_t g[8], h[8];
+      for (int k = 0; k < 8; k++) { g[k] = gh[k]; h[k] = gh[8 + k]; }
+      uint32_t m[3][50];
+      const bool got = challenge_masks_ctx32(m, g, h);
+      for (int j = 0; j < 3; j++)
+        for (int k = 0; k < 50; k++) d->c32[j][k] = got ? m[j][k] : 0;  // a host row is zero-initialised
+      c32_ok[lane] = got ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  if (live && w == 0) d->fast_ctx32 = pre_ctx32 && c32_ok[lane] ? 1 : 0;
+}
+
 constexpr int kChallengeBlock = 128;
 
 // Generic transcript tail: the byte-wise STROBE code on this thread's dword-interleaved
@@ -609,6 +688,20 @@ hipError_t launch_pair_setup(const uint32_t* gh_words, int npairs, PairSetup* ou
   return hipGetLastError();
 }
 
+hipError_t launch_pair_desc(const uint32_t* gh_words, int npairs, const uint32_t k1[50], const uint32_t k2[50],
+                            bool masks, PairDesc* desc, int32_t* ok, ge_niels* pts, hipStream_t st) {
+  if (npairs <= 0) return hipSuccess;
+  PairDescConsts km;
+  for (int k = 0; k < 50; k++) {
+    km.k1[k] = k1[k];
+    km.k2[k] = k2[k];
+  }
+  km.masks = masks ? 1 : 0;
+  hipLaunchKernelGGL(k_pair_desc, dim3((unsigned)((npairs + kPairDescPairs - 1) / kPairDescPairs)), dim3(64 * 4), 0, st,
+                     gh_words, npairs, km, desc, ok, pts);
+  return hipGetLastError();
+}
+
 hipError_t launch_challenge_pairs(const ChallengeArgs& a, const PairArgs& pa, hipStream_t st) {
   if (a.n <= 0) return hipSuccess;
   if (!pa.desc || !pa.pair_idx || a.ctx_end) return hipErrorInvalidValue;
@@ -618,11 +711,11 @@ hipError_t launch_challenge_pairs(const ChallengeArgs& a, const PairArgs& pa, hi
 }
 
 bool challenge_prefix_is_fixed(const StrobeSnap& snap) {
-  return snap.pos == kTailPrefixPos && snap.pos_begin == kTailPrefixBegin && snap.flags == kTailPrefixFlags;
+  return prefix_at_fixed(snap.pos, snap.pos_begin, snap.flags);
 }
 
 bool challenge_prefix_is_ctx32(const StrobeSnap& snap) {
-  return snap.pos == kC32PrefixPos && snap.pos_begin == kC32PrefixBegin && snap.flags == kC32PrefixFlags;
+  return prefix_at_ctx32(snap.pos, snap.pos_begin, snap.flags);
 }
 
 hipError_t launch_challenge(const ChallengeArgs& a, hipStream_t st) {

@@ -252,7 +252,24 @@ struct RlcPairExtra {
   int64_t lo, hi;
   const ge_niels* gh;
   int npairs;
+  // The batch's entries bucketed by pair (launch_pair_bucket; more than CPZ_PAIRS_MAX pairs).  With
+  // `list` set the extras come from k_pair_unit_sums / k_pair_finish over these lists, in
+  // O(n + npairs), instead of k_rlc_extra_pairs' pass over the whole range per pair.
+  const uint32_t* list = nullptr;    // [n] entry ids, pair p's at list[start[p] .. start[p + 1])
+  const uint32_t* start = nullptr;   // [npairs + 1] exclusive scan of the pairs' entry counts
+  const uint32_t* ustart = nullptr;  // [npairs + 1] exclusive scan of their unit counts (pair_sum.h)
+  sc* upart = nullptr;               // [max_units][2] scratch: the units' partial sums
+  int64_t max_units = 0;             // pair_sum_max_units(n, npairs)
 };
+// Buckets the entry ids 0 .. n - 1 by pair_idx (histogram, exclusive scan, scatter) into list /
+// start / ustart above; `cursor` is scratch of npairs + 1 words.  The order inside a pair's list
+// is not fixed, which does not matter: addition mod l is exact.  npairs <= kPairBucketMaxPairs.
+constexpr int kPairBucketMaxPairs = 4096;
+hipError_t launch_pair_bucket(const uint32_t* pair_idx, int64_t n, int npairs, uint32_t* list, uint32_t* start,
+                              uint32_t* ustart, uint32_t* cursor, hipStream_t st);
+// The extras alone (what launch_rlc_msm runs first for a px with lists): points e0 + 2 p,
+// e0 + 2 p + 1 and their digits for the range [px.lo, px.hi).
+hipError_t launch_pair_sums(const RlcMsmArgs& a, const RlcPairExtra& px, hipStream_t st);
 // Sort and accumulation geometry for `npts` MSM points: sets a.groups / a.chunk / a.echunk.
 void rlc_sort_geometry(RlcMsmArgs& a, int64_t npts);
 // marks (optional, timing): kRlcMsmMarks events recorded on `st` at the phase boundaries

@@ -39,6 +39,7 @@
 #include <cstdlib>
 
 #include "fe16.h"
+#include "pair_sum.h"
 #include "rlc.h"
 #include "rlc_dev.h"
 #include "verify.h"
@@ -358,6 +359,202 @@ __global__ void __launch_bounds__(256) k_rlc_extra_pairs(RlcMsmArgs a, RlcPairEx
 #pragma unroll
     for (int wv = 0; wv < kRlcWindows; wv++) a.digits[(int64_t)wv * a.dstride + j] = d[wv];
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// Mixed-pair batches over more than CPZ_PAIRS_MAX pairs (cpz_verify_batch_pairs_many): the same
+// extras in O(n + npairs).  Once per batch the entry ids are bucketed by pair --
+//   k_pair_hist     block-local LDS counts of kPairBucketChunk entries, then one global add per
+//                   block and touched pair
+//   k_pair_scan     one workgroup: exclusive scans of the counts (start) and of the pairs' unit
+//                   counts (ustart, pair_sum.h); the cursors start at `start`
+//   k_pair_scatter  the same block-local counts reserve each block's slice of every touched
+//                   pair's list with one global add, LDS atomics rank the entries inside it
+// -- and per MSM range [lo, hi)
+//   k_pair_unit_sums  a wave per unit of at most kPairSumUnit list entries adds the products of
+//                     those inside the range (sc_add, an LDS tree): a pair holding most of the
+//                     batch is many units, not one wave's loop
+//   k_pair_finish     workgroup p adds pair p's unit partials and writes what k_rlc_extra_pairs
+//                     writes: the points e0 + 2 p, e0 + 2 p + 1 and the sums' digits.
+// Only integer counters are touched by atomics; the scalars are added in trees, and addition mod l
+// is exact, so the sums do not depend on the order the scatter leaves.
+// ---------------------------------------------------------------------------------------
+constexpr int kPairBucketChunk = 4096;  // entries per k_pair_hist / k_pair_scatter workgroup
+
+__global__ void __launch_bounds__(256) k_pair_hist(const uint32_t* __restrict__ pair_idx, int64_t n, int npairs,
+                                                   uint32_t* __restrict__ count) {
+  __shared__ uint32_t cnt[kPairBucketMaxPairs];
+  for (int p = threadIdx.x; p < npairs; p += 256) cnt[p] = 0;
+  __syncthreads();
+  const int64_t i0 = (int64_t)blockIdx.x * kPairBucketChunk;
+  const int64_t i1 = i0 + kPairBucketChunk < n ? i0 + kPairBucketChunk : n;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) atomicAdd(&cnt[pair_idx[i]], 1u);
+  __syncthreads();
+  for (int p = threadIdx.x; p < npairs; p += 256)
+    if (cnt[p]) atomicAdd(&count[p], cnt[p]);
+}
+
+// count (in `cursor`) -> start, ustart, and cursor = start.  1024 threads, four pairs each.
+__global__ void __launch_bounds__(1024) k_pair_scan(int npairs, uint32_t* __restrict__ start,
+                                                    uint32_t* __restrict__ ustart, uint32_t* __restrict__ cursor) {
+  static_assert(kPairBucketMaxPairs == 4 * 1024, "four pairs per thread of one workgroup");
+  __shared__ uint32_t sa[1024];
+  __shared__ uint32_t sb[1024];
+  const int t = threadIdx.x;
+  uint32_t c[4], u[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int p = 4 * t + k;
+    c[k] = p < npairs ? cursor[p] : 0;
+    u[k] = pair_sum_units(c[k]);
+  }
+  sa[t] = c[0] + c[1] + c[2] + c[3];
+  sb[t] = u[0] + u[1] + u[2] + u[3];
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    const uint32_t va = t >= off ? sa[t - off] : 0, vb = t >= off ? sb[t - off] : 0;
+    __syncthreads();
+    sa[t] += va;
+    sb[t] += vb;
+    __syncthreads();
+  }
+  uint32_t ea = t ? sa[t - 1] : 0, eb = t ? sb[t - 1] : 0;  // exclusive
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int p = 4 * t + k;
+    if (p <= npairs) {  // p == npairs: the totals
+      start[p] = ea;
+      ustart[p] = eb;
+      cursor[p] = ea;
+    }
+    ea += c[k];
+    eb += u[k];
+  }
+  if (t == 1023 && npairs == kPairBucketMaxPairs) {
+    start[npairs] = ea;
+    ustart[npairs] = eb;
+    cursor[npairs] = ea;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_pair_scatter(const uint32_t* __restrict__ pair_idx, int64_t n, int npairs,
+                                                      uint32_t* __restrict__ cursor, uint32_t* __restrict__ list) {
+  __shared__ uint32_t cnt[kPairBucketMaxPairs];
+  __shared__ uint32_t base[kPairBucketMaxPairs];
+  for (int p = threadIdx.x; p < npairs; p += 256) cnt[p] = 0;
+  __syncthreads();
+  const int64_t i0 = (int64_t)blockIdx.x * kPairBucketChunk;
+  const int64_t i1 = i0 + kPairBucketChunk < n ? i0 + kPairBucketChunk : n;
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) atomicAdd(&cnt[pair_idx[i]], 1u);
+  __syncthreads();
+  for (int p = threadIdx.x; p < npairs; p += 256) {
+    if (cnt[p]) base[p] = atomicAdd(&cursor[p], cnt[p]);  // this block's slice of pair p's list
+    cnt[p] = 0;
+  }
+  __syncthreads();
+  for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) {
+    const uint32_t p = pair_idx[i];
+    list[base[p] + atomicAdd(&cnt[p], 1u)] = (uint32_t)i;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_pair_unit_sums(RlcPairExtra x) {
+  __shared__ sc red_a[256];
+  __shared__ sc red_b[256];
+  const int lane = threadIdx.x & 63;
+  const uint32_t u = blockIdx.x * 4u + (threadIdx.x >> 6);
+  const bool live = u < x.ustart[x.npairs];
+  sc sa, sb;
+#pragma unroll
+  for (int k = 0; k < 8; k++) { sa.w[k] = 0; sb.w[k] = 0; }
+  if (live) {
+    const int p = pair_sum_find(x.ustart, x.npairs, u);
+    const uint32_t j0 = x.start[p] + (u - x.ustart[p]) * (uint32_t)kPairSumUnit;
+    const uint32_t j1 = j0 + kPairSumUnit < x.start[p + 1] ? j0 + kPairSumUnit : x.start[p + 1];
+    for (uint32_t j = j0 + lane; j < j1; j += 64) {
+      const int64_t i = x.list[j];
+      if (i < x.lo || i >= x.hi) continue;
+      sa = sc_add(sa, x.prod[2 * i]);
+      sb = sc_add(sb, x.prod[2 * i + 1]);
+    }
+  }
+  red_a[threadIdx.x] = sa;
+  red_b[threadIdx.x] = sb;
+  __syncthreads();
+  for (int off = 32; off > 0; off >>= 1) {  // every wave its own 64 rows
+    if (lane < off) {
+      red_a[threadIdx.x] = sc_add(red_a[threadIdx.x], red_a[threadIdx.x + off]);
+      red_b[threadIdx.x] = sc_add(red_b[threadIdx.x], red_b[threadIdx.x + off]);
+    }
+    __syncthreads();
+  }
+  if (live && lane == 0) {
+    x.upart[2 * (int64_t)u] = red_a[threadIdx.x];
+    x.upart[2 * (int64_t)u + 1] = red_b[threadIdx.x];
+  }
+}
+
+__global__ void __launch_bounds__(64) k_pair_finish(RlcMsmArgs a, RlcPairExtra x) {
+  __shared__ sc red_a[64];
+  __shared__ sc red_b[64];
+  const uint32_t p = blockIdx.x;
+  sc sa, sb;
+#pragma unroll
+  for (int k = 0; k < 8; k++) { sa.w[k] = 0; sb.w[k] = 0; }
+  const uint32_t u1 = x.ustart[p + 1];
+  for (uint32_t u = x.ustart[p] + threadIdx.x; u < u1; u += 64) {
+    sa = sc_add(sa, x.upart[2 * (int64_t)u]);
+    sb = sc_add(sb, x.upart[2 * (int64_t)u + 1]);
+  }
+  red_a[threadIdx.x] = sa;
+  red_b[threadIdx.x] = sb;
+  __syncthreads();
+  for (int off = 32; off > 0; off >>= 1) {
+    if (threadIdx.x < off) {
+      red_a[threadIdx.x] = sc_add(red_a[threadIdx.x], red_a[threadIdx.x + off]);
+      red_b[threadIdx.x] = sc_add(red_b[threadIdx.x], red_b[threadIdx.x + off]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 2) {
+    const sc s = threadIdx.x == 0 ? red_a[0] : red_b[0];
+    const int64_t j = a.e0 + 2 * (int64_t)p + threadIdx.x;
+    {  // the point as it stands, 16 bytes at a time, as k_rlc_extra_pairs copies it
+      const uint4* src = reinterpret_cast<const uint4*>(x.gh + 2 * p + threadIdx.x);
+      uint4* dst = reinterpret_cast<uint4*>(a.pts + j);
+#pragma unroll
+      for (int k = 0; k < (int)(sizeof(ge_niels) / 16); k++) dst[k] = src[k];
+    }
+    int16_t d[kRlcWindows];
+    recode16(d, s.w);
+#pragma unroll
+    for (int wv = 0; wv < kRlcWindows; wv++) a.digits[(int64_t)wv * a.dstride + j] = d[wv];
+  }
+}
+
+hipError_t launch_pair_bucket(const uint32_t* pair_idx, int64_t n, int npairs, uint32_t* list, uint32_t* start,
+                              uint32_t* ustart, uint32_t* cursor, hipStream_t st) {
+  if (n <= 0 || n > 0xffffffffll || npairs <= 0 || npairs > kPairBucketMaxPairs) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(cursor, 0, ((size_t)npairs + 1) * sizeof(uint32_t), st);
+  if (e != hipSuccess) return e;
+  const unsigned blocks = (unsigned)((n + kPairBucketChunk - 1) / kPairBucketChunk);
+  hipLaunchKernelGGL(k_pair_hist, dim3(blocks), dim3(256), 0, st, pair_idx, n, npairs, cursor);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, npairs, start, ustart, cursor);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pair_scatter, dim3(blocks), dim3(256), 0, st, pair_idx, n, npairs, cursor, list);
+  return hipGetLastError();
+}
+
+hipError_t launch_pair_sums(const RlcMsmArgs& a, const RlcPairExtra& px, hipStream_t st) {
+  if (!px.list || !px.start || !px.ustart || !px.upart || px.max_units <= 0 || px.npairs <= 0 ||
+      px.npairs > kPairBucketMaxPairs || a.nextra != 2 * px.npairs)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_pair_unit_sums, dim3((unsigned)((px.max_units + 3) / 4)), dim3(256), 0, st, px);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pair_finish, dim3((unsigned)px.npairs), dim3(64), 0, st, a, px);
+  return hipGetLastError();
 }
 
 // point index for flat position t over [p0, p1) U [e0, e0 + nextra)
@@ -1171,7 +1368,11 @@ hipError_t launch_rlc_msm(const RlcMsmArgs& a, const sc* block_sums, int64_t b0,
   if ((e = mark(0)) != hipSuccess) return e;
   if (px) {
     if (px->npairs <= 0 || a.nextra != 2 * px->npairs) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_rlc_extra_pairs, dim3((unsigned)px->npairs), dim3(256), 0, st, a, *px);
+    if (px->list) {
+      if ((e = launch_pair_sums(a, *px, st)) != hipSuccess) return e;
+    } else {
+      hipLaunchKernelGGL(k_rlc_extra_pairs, dim3((unsigned)px->npairs), dim3(256), 0, st, a, *px);
+    }
   } else {
     if (a.nextra != 2) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_rlc_extra, dim3(1), dim3(256), 0, st, a, block_sums, b0, b1, tab);

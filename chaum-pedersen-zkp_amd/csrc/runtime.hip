@@ -21,6 +21,7 @@
 
 #include "../../include/cpz.h"
 #include "cpz_kernels.h"
+#include "pair_sum.h"
 #include "rlc.h"
 #include "verify.h"
 
@@ -261,6 +262,9 @@ struct cpz_ctx {
   // k_pair_setup leaves per pair, their Niels points, and -- once a failing batch reaches its
   // first leaf -- the descriptor table with the resident sets' tables
   DevBuf bp_gh, bp_setup, bp_pts, bp_desc;
+  // cpz_verify_batch_pairs_many: the decode flags, the entries bucketed by pair (list; start,
+  // ustart and the cursors in bp_scan), and the units' partial sums
+  DevBuf bp_ok, bp_list, bp_scan, bp_upart;
   DevBuf bp_word;  // cpz_verify_each_pairs_device: the index check's word (k_pair_idx_check)
   DevBuf pp_idx;   // cpz_prove_pairs: the call's pair indices (its descriptors go to bp_desc)
   // load_pairs, one block: the pass's destinations and encodings, its level bases, what comes back
@@ -2179,7 +2183,9 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
     b->release();
   ctx->rl_flags.release();
   ctx->rl_parts.release();
-  for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc, &ctx->bp_word, &ctx->pp_idx}) b->release();
+  for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc, &ctx->bp_word, &ctx->pp_idx, &ctx->bp_ok,
+                    &ctx->bp_list, &ctx->bp_scan, &ctx->bp_upart})
+    b->release();
 #if defined(CPZ_CLOCK_PROBE)
   for (DevBuf& b : ctx->clk) b.release();
 #endif
@@ -2934,6 +2940,13 @@ constexpr int64_t kPairRoom = (2 * CPZ_PAIRS_MAX + 3) / 4;
 static_assert(4ll * (CPZ_BATCH_PAIRS_MAX_PROOFS + kPairRoom) + 2 <= cpz::kRlcMaxMsmPoints,
               "a mixed-pair MSM exceeds the sort-entry format");
 static_assert(CPZ_BATCH_PAIRS_MAX_PROOFS + kPairRoom <= CPZ_RLC_SPAN, "a mixed-pair batch is one MSM span");
+// cpz_verify_batch_pairs_many: the same room for CPZ_BATCH_PAIRS_MANY_MAX pairs.
+constexpr int64_t kPairRoomMany = (2 * CPZ_BATCH_PAIRS_MANY_MAX + 3) / 4;
+static_assert(4ll * (CPZ_BATCH_PAIRS_MAX_PROOFS + kPairRoomMany) + 2 <= cpz::kRlcMaxMsmPoints,
+              "a mixed-pair MSM over CPZ_BATCH_PAIRS_MANY_MAX pairs exceeds the sort-entry format");
+static_assert(CPZ_BATCH_PAIRS_MAX_PROOFS + kPairRoomMany <= CPZ_RLC_SPAN,
+              "a mixed-pair batch over CPZ_BATCH_PAIRS_MANY_MAX pairs is one MSM span");
+static_assert(CPZ_BATCH_PAIRS_MANY_MAX <= cpz::kPairBucketMaxPairs, "the bucketing kernels' LDS counters");
 
 // One mixed-pair batch in progress: its staged rows and contexts, the table-less descriptors
 // and indices on the device, and what the fallback needs to make the pairs resident.
@@ -2951,6 +2964,15 @@ struct PairBatch {
   const cpz::PairDesc* d_full = nullptr;  // device descriptors with tables, set at the first leaf
   const uint8_t* seed = nullptr;          // the weights' keys (the partitioned search's locate pass)
   uint64_t first_index = 0;
+  int64_t room = kPairRoom;               // proofs of room both RLC sets hold for the pairs' points
+  // more than CPZ_PAIRS_MAX pairs (cpz_verify_batch_pairs_many): the entries bucketed by pair for
+  // the per-range sums (RlcPairExtra), and the device descriptor array the leaves patch
+  const uint32_t* d_list = nullptr;
+  const uint32_t* d_start = nullptr;
+  const uint32_t* d_ustart = nullptr;
+  cpz::sc* d_upart = nullptr;
+  int64_t max_units = 0;
+  cpz::PairDesc* d_desc = nullptr;
 };
 
 // The MSM over proofs [lo, hi) (lo a multiple of kRlcPrepBlock) of the prepared mixed-pair batch:
@@ -2958,9 +2980,9 @@ struct PairBatch {
 int pairs_range_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
   cpz::RlcMsmArgs m;
   if (int rc = rlc_msm_args(ctx->rl_prep, ctx->rl_msm, lo, hi, m)) return rc;
-  if (ctx->rl_prep.cap < b.n + kPairRoom || ctx->rl_msm.cap < (hi - lo) + kPairRoom)
+  if (ctx->rl_prep.cap < b.n + b.room || ctx->rl_msm.cap < (hi - lo) + b.room || 2 * (int64_t)b.npairs > 4 * b.room)
     return fail(CPZ_EINVAL, "internal: RLC sets reserved without room for the pairs' points");
-  m.e0 = 4 * (ctx->rl_prep.cap - kPairRoom);
+  m.e0 = 4 * (ctx->rl_prep.cap - b.room);
   m.nextra = 2 * (int)b.npairs;
   cpz::rlc_sort_geometry(m, (m.p1 - m.p0) + m.nextra);
   cpz::RlcPairExtra px;
@@ -2970,6 +2992,11 @@ int pairs_range_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi,
   px.hi = hi;
   px.gh = static_cast<const cpz::ge_niels*>(ctx->bp_pts.p);
   px.npairs = (int)b.npairs;
+  px.list = b.d_list;  // null up to CPZ_PAIRS_MAX pairs: k_rlc_extra_pairs
+  px.start = b.d_start;
+  px.ustart = b.d_ustart;
+  px.upart = b.d_upart;
+  px.max_units = b.max_units;
   StageTimer t(ctx, 3, st);
   CPZ_HIP(cpz::launch_rlc_msm(m, nullptr, 0, 0, nullptr, st, nullptr, nullptr, nullptr, &px));
   return CPZ_OK;
@@ -2991,9 +3018,17 @@ int pairs_resident(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
   return CPZ_OK;
 }
 
+int pairs_verify_range(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st);
+
 int pairs_leaf(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
   if (int rc = pairs_resident(ctx, b, st)) return rc;
   ctx->fb_stats[4] += (uint64_t)(hi - lo);
+  return pairs_verify_range(ctx, b, lo, hi, st);
+}
+
+// pairs_leaf's launches over [lo, hi): every pair an entry of the range reads has its tables in
+// b.d_full's row.
+int pairs_verify_range(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
   // a dense range: the chunked eight-lane path (CPZ_PAIRS_LEAF_QUAD=0 in the environment, read at
   // every call, restores the serial latency launches: for measurement, tools/pairs_bulk_ab.py)
   const char* leaf_quad = std::getenv("CPZ_PAIRS_LEAF_QUAD");
@@ -3294,6 +3329,94 @@ int pairs_fallback(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream
   return CPZ_OK;
 }
 
+// ---- more than CPZ_PAIRS_MAX pairs (cpz_verify_batch_pairs_many) ----------------------------
+// The bisection needs no table (pairs_range_launch with the bucketed lists); only the ranges
+// verified per proof do, and they take them CPZ_PAIRS_MAX pairs at a time.
+struct ManyRuns {
+  std::vector<uint32_t> stamp;  // per pair: the last run (or count) that saw it (pair_run_end)
+  uint32_t tag = 0;
+  std::vector<uint8_t> rows;            // a run's (g, h) rows, gathered
+  std::vector<cpz::PairDesc> full;      // and their descriptors with tables
+  bool deep = false;                    // keep bisecting below CPZ_PAIRS_MAX_PROOFS (see pairs_many_fallback)
+};
+
+// Per-proof verification of [lo, hi): consecutive runs of at most CPZ_PAIRS_MAX distinct pairs,
+// each with its pairs made resident in one pass (load_pairs: stage 13, counted per set built) and
+// verified by pairs_leaf's kernels under the global indices.
+int pairs_many_leaf(cpz_ctx* ctx, PairBatch& b, ManyRuns& ms, int64_t lo, int64_t hi, hipStream_t st) {
+  static_assert(offsetof(cpz::PairDesc, tab) == 0 && offsetof(cpz::PairDesc, tab16) == sizeof(void*) &&
+                    offsetof(cpz::PairDesc, prefix) == 2 * sizeof(void*),
+                "a row's table pointers are its first 16 bytes");
+  ctx->fb_stats[4] += (uint64_t)(hi - lo);
+  uint32_t run[CPZ_PAIRS_MAX];
+  for (int64_t a = lo; a < hi;) {
+    int k = 0;
+    const int64_t e = cpz::pair_run_end(b.pair_idx, a, hi, ms.stamp.data(), ++ms.tag, CPZ_PAIRS_MAX, run, &k);
+    for (int j = 0; j < k; j++) std::memcpy(ms.rows.data() + 64 * j, b.pairs + 64 * (size_t)run[j], 64);
+    // (decoded: k_pair_desc decoded every pair of the call before anything was staged)
+    if (int rc = load_pairs(ctx, (size_t)k, ms.rows.data(), ms.full.data(), true, nullptr)) return rc;
+    // The run's rows alone get their table pointers.  A row of a pair outside this run may hold
+    // a stale pointer from an earlier run whose set has been evicted since: no entry of [a, e)
+    // reads it, because every pair_idx of the run is one of run[0 .. k).
+    for (int j = 0; j < k; j++)
+      CPZ_HIP(hipMemcpyAsync(b.d_desc + run[j], &ms.full[(size_t)j], 2 * sizeof(void*), hipMemcpyHostToDevice, st));
+    CPZ_HIP(hipStreamSynchronize(st));  // a pageable source
+    if (int rc = pairs_verify_range(ctx, b, a, e, st)) return rc;
+    CPZ_HIP(hipStreamSynchronize(st));  // the next run's load_pairs may evict these sets
+    a = e;
+  }
+  return CPZ_OK;
+}
+
+// More than CPZ_PAIRS_MAX distinct pairs among the entries [lo, hi)?
+bool pairs_many_distinct_over(const PairBatch& b, ManyRuns& ms, int64_t lo, int64_t hi) {
+  uint32_t run[CPZ_PAIRS_MAX];
+  int k = 0;
+  return cpz::pair_run_end(b.pair_idx, lo, hi, ms.stamp.data(), ++ms.tag, CPZ_PAIRS_MAX, run, &k) < hi;
+}
+
+// pairs_fallback without the partitioned branch (part.hip's lists hold CPZ_PAIRS_MAX pairs).
+// ms.deep (the default): a range of at most CPZ_PAIRS_MAX_PROOFS entries that still holds more than
+// CPZ_PAIRS_MAX distinct pairs is bisected further, down to single weight blocks, instead of being
+// verified in runs -- a sub-range MSM costs less than the table sets of the pairs it clears.
+// CPZ_PAIRS_MANY_DEEP=0 in the environment, read at every call, stops at CPZ_PAIRS_MAX_PROOFS as
+// pairs_fallback does: for measurement (tools/batch_pairs_many_ab.py).
+int pairs_many_fallback(cpz_ctx* ctx, PairBatch& b, ManyRuns& ms, int64_t lo, int64_t hi, hipStream_t st, int depth) {
+  bool leaf = hi - lo <= (int64_t)CPZ_PAIRS_MAX_PROOFS || depth > 12;
+  if (leaf && ms.deep && depth <= 12 && hi - lo > (int64_t)cpz::kRlcPrepBlock && pairs_many_distinct_over(b, ms, lo, hi))
+    leaf = false;
+  if (leaf) return pairs_many_leaf(ctx, b, ms, lo, hi, st);
+  int64_t cuts[kFanout + 1];
+  for (int k = 0; k <= kFanout; k++) {
+    int64_t c = lo + ((hi - lo) * k) / kFanout;
+    c = (c / cpz::kRlcPrepBlock) * cpz::kRlcPrepBlock;
+    cuts[k] = k == 0 ? lo : (k == kFanout ? hi : (c < lo ? lo : c));
+  }
+  // at most kFanout weight blocks (the deep policy alone gets here): a part per block, so that a
+  // range just above one block is still cut (lo is a multiple of the block)
+  if (hi - lo <= (int64_t)kFanout * cpz::kRlcPrepBlock)
+    for (int k = 1; k <= kFanout; k++) cuts[k] = std::min<int64_t>(lo + (int64_t)k * cpz::kRlcPrepBlock, hi);
+  bool failing[kFanout];
+  int nfail = 0;
+  for (int k = 0; k < kFanout; k++) {
+    failing[k] = false;
+    if (cuts[k + 1] <= cuts[k]) continue;
+    if (int rc = pairs_range_launch(ctx, b, cuts[k], cuts[k + 1], st)) return rc;
+    int ident = 0;
+    CPZ_HIP(hipMemcpyAsync(&ident, ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+    ctx->fb_stats[5] += 1;
+    failing[k] = !ident;
+    nfail += failing[k] ? 1 : 0;
+  }
+  if (2 * nfail > kFanout) return pairs_many_leaf(ctx, b, ms, lo, hi, st);  // dense failures: no pruning left
+  for (int k = 0; k < kFanout; k++) {
+    if (!failing[k]) continue;
+    if (int rc = pairs_many_fallback(ctx, b, ms, cuts[k], cuts[k + 1], st, depth + 1)) return rc;
+  }
+  return CPZ_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3434,7 +3557,7 @@ int cpz_verify_batch_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const
     CPZ_HIP(cpz::launch_challenge_pairs(ca, pa, st));
   }
   if ((rc = rlc_prepare_points(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], b.d_status, seed, first_index, st, true,
-                               kPairRoom)))
+                               b.room)))
     return rc;
   if ((rc = pairs_range_launch(ctx, b, 0, (int64_t)n, st))) return rc;
   // the partial, its identity flag, the any-bad word and the statuses with one synchronisation;
@@ -3457,6 +3580,164 @@ int cpz_verify_batch_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const
       rc = pairs_fallback(ctx, b, 0, (int64_t)n, st, 0);
     }
     if (rc) return rc;
+    CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+  }
+  std::memcpy(partial_out, part, 32);
+  *batch_ok = (ident && words[1] == 0) ? 1 : 0;
+  if (status_out) std::memcpy(status_out, st_host.data(), n);
+  return CPZ_OK;
+}
+
+int cpz_verify_batch_pairs_many(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
+                                const uint32_t* pair_idx, const uint8_t* y1, const uint8_t* y2, const uint8_t* r1,
+                                const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                                const uint8_t* ctx_present, const uint8_t seed[32], uint64_t first_index,
+                                uint8_t partial_out[32], int* batch_ok, uint8_t* status_out) {
+  // up to CPZ_PAIRS_MAX pairs this is cpz_verify_batch_pairs_ex itself: same route, same timing
+  if (npairs <= CPZ_PAIRS_MAX)
+    return cpz_verify_batch_pairs_ex(ctx, flags, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, ctx_bytes, ctx_off,
+                                     ctx_present, seed, first_index, partial_out, batch_ok, status_out);
+  // its checks, in its order and wording
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+  if (npairs > CPZ_BATCH_PAIRS_MANY_MAX)
+    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_BATCH_PAIRS_MANY_MAX (" +
+                                std::to_string(CPZ_BATCH_PAIRS_MANY_MAX) + ")");
+  if (n > CPZ_BATCH_PAIRS_MAX_PROOFS)
+    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_BATCH_PAIRS_MAX_PROOFS (" +
+                                std::to_string(CPZ_BATCH_PAIRS_MAX_PROOFS) + ")");
+  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !seed || !partial_out || !batch_ok)
+    return fail(CPZ_EINVAL, "null input pointer");
+  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  for (size_t i = 0; i < n; i++)
+    if (pair_idx[i] >= npairs)
+      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
+                                  " is not below npairs (" + std::to_string(npairs) + ")");
+  static const uint8_t zero[32] = {0};
+  for (size_t p = 0; p < npairs; p++) {
+    const uint8_t *g = pairs + 64 * p, *h = g + 32;
+    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
+    if (std::memcmp(g, h, 32) == 0)
+      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
+  }
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  for (auto& v : ctx->fb_stats) v = 0;
+  hipStream_t st = ctx->stream;
+  int rc = order_after_last(ctx, st);
+  if (rc) return rc;
+  // Per-pair set-up on the device: the table-less descriptor rows, the pairs' Niels points and
+  // the decode flags, which alone come back (timed inside stage 2, as k_pair_setup is).
+  CPZ_HIP(ctx->bp_gh.ensure(npairs * 64));
+  CPZ_HIP(ctx->bp_ok.ensure(npairs * 2 * sizeof(int32_t)));
+  CPZ_HIP(ctx->bp_pts.ensure(2 * npairs * sizeof(cpz::ge_niels)));
+  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
+  std::vector<int32_t> ok(2 * npairs);
+  {
+    uint32_t k1[50], k2[50];
+    const bool masks = cpz::challenge_masks(k1, k2);  // the same for every pair: once, here
+    StageTimer t(ctx, 2, st);
+    CPZ_HIP(hipMemcpyAsync(ctx->bp_gh.p, pairs, npairs * 64, hipMemcpyHostToDevice, st));
+    CPZ_HIP(cpz::launch_pair_desc(static_cast<const uint32_t*>(ctx->bp_gh.p), (int)npairs, k1, k2, masks,
+                                  static_cast<cpz::PairDesc*>(ctx->bp_desc.p), static_cast<int32_t*>(ctx->bp_ok.p),
+                                  static_cast<cpz::ge_niels*>(ctx->bp_pts.p), st));
+    CPZ_HIP(hipMemcpyAsync(ok.data(), ctx->bp_ok.p, ok.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
+  CPZ_HIP(hipStreamSynchronize(st));
+  for (size_t p = 0; p < npairs; p++)
+    if (!ok[2 * p] || !ok[2 * p + 1])
+      return fail(CPZ_EGENERATOR,
+                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
+  // the indices go to the device in one block with the rows (stage_inputs' extra)
+  const uint8_t* host[5] = {y1, y2, r1, r2, s};
+  const void* dev[5];
+  const void* dcb;
+  const uint64_t* dco;
+  const uint8_t* dcp;
+  const void* dex = nullptr;
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, false, nullptr, nullptr,
+                    pair_idx, n * sizeof(uint32_t), &dex);
+  if (rc) return rc;
+  if (!dex) return fail(CPZ_EHIP, "internal: the pair indices were not staged");
+  CPZ_HIP(ctx->st.ensure(n));
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  PairBatch b;
+  b.npairs = npairs;
+  b.n = (int64_t)n;
+  b.pairs = pairs;
+  b.pair_idx = pair_idx;
+  for (int k = 0; k < 5; k++) b.rows[k] = dev[k];
+  b.cb = dcb;
+  b.co = dco;
+  b.cp = dcp;
+  b.d_idx = static_cast<const uint32_t*>(dex);
+  b.d_status = static_cast<uint8_t*>(ctx->st.p);
+  b.d_desc = static_cast<cpz::PairDesc*>(ctx->bp_desc.p);
+  b.d_full = b.d_desc;  // the leaves patch the tables of the pairs they read into these rows
+  b.seed = seed;
+  b.first_index = first_index;
+  b.room = kPairRoomMany;
+  // the entries bucketed by pair, once per batch (the sort phase's accounting: stage 3)
+  b.max_units = cpz::pair_sum_max_units((int64_t)n, (int64_t)npairs);
+  CPZ_HIP(ctx->bp_list.ensure(n * sizeof(uint32_t)));
+  CPZ_HIP(ctx->bp_scan.ensure(3 * (npairs + 1) * sizeof(uint32_t)));
+  CPZ_HIP(ctx->bp_upart.ensure((size_t)b.max_units * 2 * sizeof(cpz::sc)));
+  {
+    uint32_t* scan = static_cast<uint32_t*>(ctx->bp_scan.p);
+    b.d_list = static_cast<const uint32_t*>(ctx->bp_list.p);
+    b.d_start = scan;
+    b.d_ustart = scan + (npairs + 1);
+    b.d_upart = static_cast<cpz::sc*>(ctx->bp_upart.p);
+    StageTimer t(ctx, 3, st);
+    CPZ_HIP(cpz::launch_pair_bucket(b.d_idx, (int64_t)n, (int)npairs, static_cast<uint32_t*>(ctx->bp_list.p), scan,
+                                    scan + (npairs + 1), scan + 2 * (npairs + 1), st));
+  }
+  {
+    cpz::ChallengeArgs ca{};
+    ca.eq_only = ctx->call_eq ? 1 : 0;
+    ca.n = (int64_t)n;
+    ca.y1 = static_cast<const uint32_t*>(dev[0]);
+    ca.y2 = static_cast<const uint32_t*>(dev[1]);
+    ca.r1 = static_cast<const uint32_t*>(dev[2]);
+    ca.r2 = static_cast<const uint32_t*>(dev[3]);
+    ca.s = static_cast<const uint32_t*>(dev[4]);
+    ca.ctx_bytes = static_cast<const uint8_t*>(dcb);
+    ca.ctx_off = dco;
+    ca.ctx_present = dcp;
+    ca.prefix = nullptr;  // per pair: PairDesc
+    ca.c_out = static_cast<uint32_t*>(ctx->c.p);
+    ca.status_out = b.d_status;
+    cpz::PairArgs pa;
+    pa.desc = b.d_desc;
+    pa.pair_idx = b.d_idx;
+    StageTimer t(ctx, 0, st);
+    CPZ_HIP(cpz::launch_challenge_pairs(ca, pa, st));
+  }
+  if ((rc = rlc_prepare_points(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], b.d_status, seed, first_index, st, true,
+                               b.room)))
+    return rc;
+  if ((rc = pairs_range_launch(ctx, b, 0, (int64_t)n, st))) return rc;
+  uint8_t part[32];
+  int words[2] = {0, 0};
+  std::vector<uint8_t> st_host(status_out ? n : 0);
+  CPZ_HIP(hipMemcpyAsync(part, ctx->rl_msm.partial.p, 32, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipMemcpyAsync(&words[0], ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipMemcpyAsync(&words[1], static_cast<int*>(ctx->rl_flags.p) + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (status_out) CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  const bool ident = words[0] != 0;
+  if (!ident && status_out) {
+    // bisection, then runs; CPZ_CALL_PARTITIONED is ignored (part.hip's lists hold CPZ_PAIRS_MAX pairs)
+    ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
+    ManyRuns ms;
+    ms.stamp.assign(npairs, 0);
+    ms.rows.resize(64 * CPZ_PAIRS_MAX);
+    ms.full.resize(CPZ_PAIRS_MAX);
+    const char* deep = std::getenv("CPZ_PAIRS_MANY_DEEP");
+    ms.deep = !(deep && deep[0] == '0');
+    if ((rc = pairs_many_fallback(ctx, b, ms, 0, (int64_t)n, st, 0))) return rc;
     CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
     CPZ_HIP(hipStreamSynchronize(st));
   }

@@ -405,6 +405,35 @@ int cpz_verify_batch_pairs_ex(cpz_ctx *ctx, uint32_t flags, size_t npairs, const
                               const uint8_t *ctx_present, const uint8_t seed[32], uint64_t first_index,
                               uint8_t partial_out[32], int *batch_ok, uint8_t *status_out);
 
+/* cpz_verify_batch_pairs_ex over up to CPZ_BATCH_PAIRS_MANY_MAX (g, h) pairs in one MSM: the
+ * same arguments, partial, batch_ok and statuses -- the sum over the pairs of cpz_verify_batch's
+ * partial over that pair's entries, weights keyed by first_index + position, statuses what
+ * cpz_verify_each_pairs_ex reports under each entry's own pair -- for callers with more pairs
+ * than a context keeps resident (a tenant per entry, a bulk batch over thousands of tenants).
+ * Rows of `pairs` may repeat, may be the default pair and may have no entry; shards combine
+ * through cpz_combine_partials; CPZ_CALL_EQUATIONS_ONLY and the context's commitment-check mode
+ * apply.  npairs <= CPZ_PAIRS_MAX is cpz_verify_batch_pairs_ex itself (the call is forwarded).
+ * Above that:
+ *   - a passing batch builds no table: the descriptors are built on the device, the entries are
+ *     bucketed by pair once, and every MSM's per-pair sums cost O(n + npairs);
+ *   - a failing batch with status_out is bisected (sub-range MSMs, no table), and each range
+ *     that is verified per proof is cut into consecutive runs of at most CPZ_PAIRS_MAX distinct
+ *     pairs, whose tables are built in one pass per run (stage 13 counts the sets built) before
+ *     the run is verified;
+ *   - CPZ_CALL_PARTITIONED is ignored: the partitioned check's lists hold CPZ_PAIRS_MAX pairs,
+ *     so the route is bisection, then runs;
+ *   - cpz_ctx_fallback_stats reports CPZ_FALLBACK_NONE or _BISECTION with out[4] and out[5].
+ * Checked before anything is staged, in cpz_verify_batch_pairs_ex's order and wording,
+ * cpz_last_error naming the lowest offending pair or entry, and no output buffer is written on
+ * an error; npairs > CPZ_BATCH_PAIRS_MANY_MAX -> CPZ_EINVAL.  Host buffers only. */
+#define CPZ_BATCH_PAIRS_MANY_MAX 4096
+int cpz_verify_batch_pairs_many(cpz_ctx *ctx, uint32_t flags, size_t npairs, const uint8_t *pairs, size_t n,
+                                const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                                const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                                const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                                const uint8_t *ctx_present, const uint8_t seed[32], uint64_t first_index,
+                                uint8_t partial_out[32], int *batch_ok, uint8_t *status_out);
+
 /* What the last cpz_verify_batch[_device] or cpz_verify_batch_pairs call on the context did to
  * locate invalid entries (fallback != 0, or status_out given), for tests and benchmarks; a
  * mixed-pair batch that reaches the partitioned check in several ranges reports their totals:

@@ -53,6 +53,7 @@ pub const CPZ_PAIRS_MAX: usize = 64;
 pub const CPZ_PAIRS_MAX_PROOFS: usize = 2048;
 pub const CPZ_BATCH_PAIRS_MAX_PROOFS: usize = 1048576;
 pub const CPZ_BATCH_PAIRS_PART_MIN: usize = 524288;
+pub const CPZ_BATCH_PAIRS_MANY_MAX: usize = 4096;
 pub const CPZ_PAIRS_BULK_MAX_PROOFS: usize = 1048576;
 pub const CPZ_PROVE_PAIRS_MAX_PROOFS: usize = 1048576;
 pub const CPZ_FALLBACK_STATS: usize = 8;
@@ -114,6 +115,11 @@ extern "C" {
                                      s: *const u8, ctx_bytes: *const u8, ctx_off: *const u64, ctx_present: *const u8,
                                      seed: *const u8, first_index: u64, partial_out: *mut u8, batch_ok: *mut c_int,
                                      status_out: *mut u8) -> c_int;
+    pub fn cpz_verify_batch_pairs_many(ctx: *mut cpz_ctx, flags: u32, npairs: usize, pairs: *const u8, n: usize,
+                                       pair_idx: *const u32, y1: *const u8, y2: *const u8, r1: *const u8,
+                                       r2: *const u8, s: *const u8, ctx_bytes: *const u8, ctx_off: *const u64,
+                                       ctx_present: *const u8, seed: *const u8, first_index: u64,
+                                       partial_out: *mut u8, batch_ok: *mut c_int, status_out: *mut u8) -> c_int;
     pub fn cpz_verify_each_device(ctx: *mut cpz_ctx, g: *const u8, h: *const u8, n: usize, d_y1: *const c_void,
                                   d_y2: *const c_void, d_r1: *const c_void, d_r2: *const c_void, d_s: *const c_void,
                                   d_ctx_bytes: *const c_void, d_ctx_off: *const u64, d_ctx_present: *const u8,
