@@ -134,6 +134,55 @@ constexpr size_t kPipeChunk = size_t(1) << 17;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Contexts are offsets into a blob: offsets over a non-empty blob need the blob (host buffers;
+// null offsets: any offsets, whose values the host cannot see, for device buffers).
+int check_contexts(const void* ctx_bytes, const uint64_t* ctx_off, size_t n, bool on_device = false) {
+  if (ctx_off && !ctx_bytes && (on_device || ctx_off[n] != ctx_off[0]))
+    return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  return CPZ_OK;
+}
+
+// The five proof rows of a batch on the device (8 words per proof each; a call without a row
+// leaves it null) and its transcript contexts, as the kernels' argument structs take them.
+struct Rows {
+  const uint32_t *y1 = nullptr, *y2 = nullptr, *r1 = nullptr, *r2 = nullptr, *s = nullptr;
+  Rows() = default;
+  Rows(const void* a, const void* b, const void* c, const void* d, const void* e)
+      : y1(static_cast<const uint32_t*>(a)), y2(static_cast<const uint32_t*>(b)), r1(static_cast<const uint32_t*>(c)),
+        r2(static_cast<const uint32_t*>(d)), s(static_cast<const uint32_t*>(e)) {}
+  bool complete() const { return y1 && y2 && r1 && r2 && s; }
+  bool aligned() const { return aligned16(y1) && aligned16(y2) && aligned16(r1) && aligned16(r2) && aligned16(s); }
+  // the rows from proof a on
+  Rows at(int64_t a) const {
+    auto from = [a](const uint32_t* p) { return p ? p + 8 * a : nullptr; };
+    return Rows(from(y1), from(y2), from(r1), from(r2), from(s));
+  }
+};
+
+struct Ctxs {
+  const uint8_t* bytes = nullptr;
+  const uint64_t* off = nullptr;      // n + 1 absolute offsets into bytes, or null: no contexts
+  const uint8_t* present = nullptr;   // n flags, or null
+  Ctxs() = default;
+  Ctxs(const void* b, const uint64_t* o, const uint8_t* p) : bytes(static_cast<const uint8_t*>(b)), off(o), present(p) {}
+  // the contexts from proof a on (the offsets stay absolute)
+  Ctxs at(int64_t a) const { return Ctxs(bytes, off ? off + a : nullptr, present ? present + a : nullptr); }
+};
+
+// The row fields of a ChallengeArgs, VerifyArgs or RlcPrepArgs.
+template <class Args>
+void set_rows(Args& a, const Rows& r) {
+  a.y1 = r.y1;
+  a.y2 = r.y2;
+  a.r1 = r.r1;
+  a.r2 = r.r2;
+  a.s = r.s;
+}
+template <class Args>
+Rows rows_of(const Args& a) {
+  return Rows(a.y1, a.y2, a.r1, a.r2, a.s);
+}
+
 // partial_out of a batch check that skipped its MSM (dense fallback): 32 x 0xff, not an encoding
 bool is_no_partial(const uint8_t p[32]) {
   for (int k = 0; k < 32; k++)
@@ -380,6 +429,19 @@ GenSet* lru_victim(GenSet* sets, int n) {
   return v;
 }
 
+// Parameters::with_generators (gadgets.rs:77-103), the part the host sees without decoding: not
+// the identity, distinct.  `who` prefixes the message ("pair 3: " in a mixed-pair call).
+const char kGenNoDecode[] = "generator encoding does not decode to a ristretto255 point";
+std::string pair_tag(size_t p) { return "pair " + std::to_string(p) + ": "; }
+
+int check_generators(const uint8_t g[32], const uint8_t h[32], const std::string& who = std::string()) {
+  static const uint8_t zero[32] = {0};
+  if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
+    return fail(CPZ_EGENERATOR, who + "generator cannot be identity");
+  if (std::memcmp(g, h, 32) == 0) return fail(CPZ_EGENERATOR, who + "generators g and h must be different");
+  return CPZ_OK;
+}
+
 // The Niels tables (g, h at 2^(32 m) times, kNielsLevels levels) and transcript prefix of
 // (g, h) into e, and the fixed-schedule masks; CPZ_EGENERATOR if an encoding does not decode.
 int build_niels_prefix(cpz_ctx* ctx, GenSet& e, const uint8_t both[64]) {
@@ -403,7 +465,7 @@ int build_niels_prefix(cpz_ctx* ctx, GenSet& e, const uint8_t both[64]) {
   CPZ_HIP(hipMemcpyAsync(ok, ctx->ok_flags.p, sizeof(ok), hipMemcpyDeviceToHost, ctx->stream));
   CPZ_HIP(hipMemcpyAsync(snap, e.prefix.p, sizeof(e.snap), hipMemcpyDeviceToHost, ctx->stream));
   CPZ_HIP(hipStreamSynchronize(ctx->stream));
-  if (!ok[0] || !ok[1]) return fail(CPZ_EGENERATOR, "generator encoding does not decode to a ristretto255 point");
+  if (!ok[0] || !ok[1]) return fail(CPZ_EGENERATOR, kGenNoDecode);
   e.prefix_fixed = cpz::challenge_prefix_is_fixed(snap[1]) && cpz::challenge_masks(e.chal_k1, e.chal_k2);
   uint32_t gw[16];
   std::memcpy(gw, both, 64);
@@ -443,11 +505,7 @@ int ensure_generators(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], bo
       }
     }
   }
-  // Parameters::with_generators (gadgets.rs:77-103): valid, non-identity, distinct.
-  static const uint8_t zero[32] = {0};
-  if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
-    return fail(CPZ_EGENERATOR, "generator cannot be identity");
-  if (std::memcmp(g, h, 32) == 0) return fail(CPZ_EGENERATOR, "generators g and h must be different");
+  if (int rc = check_generators(g, h)) return rc;  // (valid: the build below decodes them)
   // a set is about to be rebuilt: no earlier call's kernels may still be reading it
   if (ctx->have_last) CPZ_HIP(hipEventSynchronize(ctx->last_done));
   GenSet& e = light ? *lru_victim(ctx->light, kLightCache) : *lru_victim(ctx->gen, ctx->gen_cap);
@@ -568,6 +626,102 @@ int64_t verify_quad_max(const cpz_ctx* ctx) {
 // variable bases (light sets), which only the eight-lane and latency kernels support: the same
 // bound as verify_quad_max, so a light-set call never reaches k_verify_each.
 int64_t var_base_max(const cpz_ctx* ctx) { return std::min<int64_t>(cpz::kVarBaseMax, verify_quad_max(ctx)); }
+// ChallengeArgs of n proofs whose pair comes with each proof (launch_challenge_pairs, the latency
+// kernels' mixed-pair siblings): no prefix, generator words or masks -- PairDesc carries them.
+cpz::ChallengeArgs pairs_challenge_args(const cpz_ctx* ctx, int64_t n, const Rows& r, const Ctxs& cx, uint32_t* c_out,
+                                        uint8_t* status_out) {
+  cpz::ChallengeArgs ca{};
+  ca.eq_only = ctx->call_eq ? 1 : 0;
+  ca.n = n;
+  set_rows(ca, r);
+  ca.ctx_bytes = cx.bytes;
+  ca.ctx_off = cx.off;
+  ca.ctx_present = cx.present;
+  ca.prefix = nullptr;
+  ca.c_out = c_out;
+  ca.status_out = status_out;
+  return ca;
+}
+
+// ChallengeArgs of n proofs under the current pair (ctx->gs): its schedules, generator words and
+// transcript prefix.
+cpz::ChallengeArgs challenge_args(const cpz_ctx* ctx, int64_t n, const Rows& r, const Ctxs& cx, uint32_t* c_out,
+                                  uint8_t* status_out) {
+  cpz::ChallengeArgs ca = pairs_challenge_args(ctx, n, r, cx, c_out, status_out);
+  set_challenge_schedules(ctx, ca);
+  words_from_bytes(ca.gh_words, ctx->gs->gh, ctx->gs->gh + 32);
+  ca.prefix = static_cast<const cpz::StrobeSnap*>(ctx->gs->prefix.p);
+  return ca;
+}
+
+// VerifyArgs of n proofs under the current pair with challenges c: its combs, or for a light set
+// (ensure_generators, n <= var_base_max) its Niels tables as variable bases.  The table slab is
+// set per launch.
+int pair_verify_args(const cpz_ctx* ctx, int64_t n, const Rows& r, const uint32_t* c, uint8_t* status,
+                     cpz::VerifyArgs& va) {
+  va = cpz::VerifyArgs{};
+  va.n = n;
+  set_rows(va, r);
+  va.c = c;
+  va.status = status;
+  va.eq_only = ctx->call_eq ? 1 : 0;
+  if (ctx->gs->full) {
+    va.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
+    return CPZ_OK;
+  }
+  if (n > var_base_max(ctx)) return fail(CPZ_EINVAL, "internal: variable-base call above var_base_max");
+  va.vtab = static_cast<const cpz::ge_niels*>(ctx->gs->tab.p);
+  va.vtab16 = static_cast<const int32_t*>(ctx->gs->tab16.p);
+  return CPZ_OK;
+}
+
+// VerifyArgs of per-proof verification under the current pair's combs over a batch whose
+// challenges are in ctx->c and whose points the prepare decoded (VerifyArgs::pre: entries with a
+// non-zero decode-level status in `status` keep it).  The table slab is set per launch.
+cpz::VerifyArgs batch_verify_args(const cpz_ctx* ctx, int64_t n, const Rows& r, uint8_t* status) {
+  cpz::VerifyArgs va{};
+  va.n = n;
+  set_rows(va, r);
+  va.c = static_cast<const uint32_t*>(ctx->c.p);
+  va.status = status;
+  va.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
+  va.pre = static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p);
+  va.eq_only = ctx->call_eq ? 1 : 0;
+  return va;
+}
+
+// VerifyArgs of the mixed-pair kernels over the proofs of ca (PairArgs brings the tables): the
+// challenges k_challenge_pairs leaves in ca.c_out, or, that being null, computed in the kernel.
+cpz::VerifyArgs pairs_verify_args(const cpz::ChallengeArgs& ca) {
+  cpz::VerifyArgs va{};
+  va.n = ca.n;
+  set_rows(va, rows_of(ca));
+  va.c = ca.c_out;
+  va.status = ca.status_out;
+  va.eq_only = ca.eq_only;
+  return va;
+}
+
+// PairArgs over a staged block of a call's npairs descriptors followed by its indices
+// (pairs_resident_block, pairs_setup_host).
+cpz::PairArgs staged_pair_args(const void* block, size_t npairs) {
+  cpz::PairArgs pa;
+  pa.desc = static_cast<const cpz::PairDesc*>(block);
+  pa.pair_idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(block) + npairs * sizeof(cpz::PairDesc));
+  return pa;
+}
+
+// va over proofs [a, a + n) of its batch.
+cpz::VerifyArgs verify_args_at(const cpz::VerifyArgs& va, int64_t a, int64_t n) {
+  cpz::VerifyArgs v = va;
+  v.n = n;
+  set_rows(v, rows_of(va).at(a));
+  if (va.c) v.c = va.c + 8 * a;
+  if (va.pre) v.pre = va.pre + 4 * a;
+  v.status = va.status + a;
+  return v;
+}
+
 // Round-robin position of the verify launches of one call that enqueues several batches
 // (the host-buffer pipeline): launches keep alternating streams across batches, and the
 // streams are joined once at the end.
@@ -575,8 +729,25 @@ struct VerifyRR {
   int64_t next = 0;
 };
 
-int join_verify_streams(cpz_ctx* ctx, hipStream_t st) {
-  for (int k = 0; k < CPZ_VERIFY_STREAMS - 1; k++) {
+// The launches of a call that alternates over nst verify streams go to `st` and the first
+// nst - 1 aux streams.  Fork: the aux streams (created on first use, with their events) start
+// after st's prior work.  nst = 1 records aux_start alone, for a caller with a stream of its own
+// to start (launch_probe).
+int fork_verify_streams(cpz_ctx* ctx, hipStream_t st, int nst) {
+  if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
+  CPZ_HIP(hipEventRecord(ctx->aux_start, st));
+  for (int k = 0; k < nst - 1; k++) {
+    if (!ctx->aux_stream[k]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[k], ctx->cus, ctx->device, &ctx->own_queues));
+    if (!ctx->aux_done[k]) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_done[k], hipEventDisableTiming));
+    CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->aux_start, 0));
+  }
+  return CPZ_OK;
+}
+
+// Join: `st` waits for the nst - 1 forked streams (the pipeline, which forks per batch and joins
+// once: all of them; one never forked because an earlier step failed is skipped).
+int join_verify_streams(cpz_ctx* ctx, hipStream_t st, int nst = CPZ_VERIFY_STREAMS) {
+  for (int k = 0; k < nst - 1; k++) {
     if (!ctx->aux_stream[k]) continue;
     CPZ_HIP(hipEventRecord(ctx->aux_done[k], ctx->aux_stream[k]));
     CPZ_HIP(hipStreamWaitEvent(st, ctx->aux_done[k], 0));
@@ -599,27 +770,11 @@ int launch_verify_chunks(cpz_ctx* ctx, const cpz::VerifyArgs& va, int stage, hip
   const int64_t chunks = (va.n + per - 1) / per;
   const int nst = rr ? CPZ_VERIFY_STREAMS : (int)std::min<int64_t>(CPZ_VERIFY_STREAMS, chunks);
   CPZ_HIP(ctx->scratch.ensure((size_t)CPZ_VERIFY_STREAMS * slab));
-  if (nst > 1) {
-    if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
-    CPZ_HIP(hipEventRecord(ctx->aux_start, st));  // the aux streams start after st's prior work
-    for (int k = 0; k < nst - 1; k++) {
-      if (!ctx->aux_stream[k]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[k], ctx->cus, ctx->device, &ctx->own_queues));
-      if (!ctx->aux_done[k]) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_done[k], hipEventDisableTiming));
-      CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->aux_start, 0));
-    }
-  }
+  if (nst > 1)
+    if (int rc = fork_verify_streams(ctx, st, nst)) return rc;
   for (int64_t c = 0; c < chunks; c++) {
     const int64_t a = c * per;
-    cpz::VerifyArgs v = va;
-    v.n = (va.n - a) < per ? (va.n - a) : per;
-    v.y1 = va.y1 + 8 * a;
-    v.y2 = va.y2 + 8 * a;
-    v.r1 = va.r1 + 8 * a;
-    v.r2 = va.r2 + 8 * a;
-    v.s = va.s + 8 * a;
-    v.c = va.c + 8 * a;
-    if (va.pre) v.pre = va.pre + 4 * a;
-    v.status = va.status + a;
+    cpz::VerifyArgs v = verify_args_at(va, a, std::min(va.n - a, per));
     v.quad_max = verify_quad_max(ctx);
 #if defined(CPZ_CLOCK_PROBE)
     CPZ_HIP(ctx->clk[3].ensure(cpz::kSmallStamps * sizeof(uint64_t)));
@@ -658,11 +813,7 @@ int launch_verify_chunks(cpz_ctx* ctx, const cpz::VerifyArgs& va, int stage, hip
     if (ca) {
       cpz::ChallengeArgs cc = *ca;
       cc.n = v.n;
-      cc.y1 = v.y1;
-      cc.y2 = v.y2;
-      cc.r1 = v.r1;
-      cc.r2 = v.r2;
-      cc.s = v.s;
+      set_rows(cc, rows_of(v));
       cc.c_out = ca->c_out + 8 * a;
       cc.status_out = ca->status_out + a;
       if (ca->ctx_off) cc.ctx_off = ca->ctx_off + a;  // absolute offsets into ctx_bytes
@@ -674,7 +825,7 @@ int launch_verify_chunks(cpz_ctx* ctx, const cpz::VerifyArgs& va, int stage, hip
     StageTimer t(ctx, stage, sc);
     CPZ_HIP(cpz::launch_verify_each(v, grid, sc));
   }
-  if (join && nst > 1) return join_verify_streams(ctx, st);
+  if (join && nst > 1) return join_verify_streams(ctx, st, nst);
   return CPZ_OK;
 }
 
@@ -682,53 +833,22 @@ int launch_verify_chunks(cpz_ctx* ctx, const cpz::VerifyArgs& va, int stage, hip
 // (default: the context's buffer from offset 0) -- launches of at most kSmallMax proofs compute
 // them inside k_verify_small / k_verify_wide and leave c_buf unwritten, so no caller may read
 // challenges back from it; rr / join: see VerifyRR; ctx_end: see ChallengeArgs.
-int enqueue_verify(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, const void* r1, const void* r2,
-                   const void* s, const void* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present,
-                   uint8_t* status, hipStream_t st, uint32_t* c_buf = nullptr, VerifyRR* rr = nullptr,
-                   bool join = true, const uint64_t* ctx_end = nullptr) {
+int enqueue_verify(cpz_ctx* ctx, size_t n, const Rows& rows, const Ctxs& cx, uint8_t* status, hipStream_t st,
+                   uint32_t* c_buf = nullptr, VerifyRR* rr = nullptr, bool join = true,
+                   const uint64_t* ctx_end = nullptr) {
   if (!c_buf) {
     CPZ_HIP(ctx->c.ensure(n * 32));
     c_buf = static_cast<uint32_t*>(ctx->c.p);
   }
-  cpz::ChallengeArgs ca;
-  set_challenge_schedules(ctx, ca);
-  ca.n = (int64_t)n;
-  words_from_bytes(ca.gh_words, ctx->gs->gh, ctx->gs->gh + 32);
-  ca.y1 = static_cast<const uint32_t*>(y1);
-  ca.y2 = static_cast<const uint32_t*>(y2);
-  ca.r1 = static_cast<const uint32_t*>(r1);
-  ca.r2 = static_cast<const uint32_t*>(r2);
-  ca.s = static_cast<const uint32_t*>(s);
-  ca.ctx_bytes = static_cast<const uint8_t*>(ctx_bytes);
-  ca.ctx_off = ctx_off;
-  ca.ctx_present = ctx_present;
+  cpz::ChallengeArgs ca = challenge_args(ctx, (int64_t)n, rows, cx, c_buf, status);
   ca.ctx_end = ctx_end;
-  ca.prefix = static_cast<const cpz::StrobeSnap*>(ctx->gs->prefix.p);
-  ca.c_out = c_buf;
-  ca.status_out = status;
   cpz::VerifyArgs va;
-  va.n = (int64_t)n;
-  va.y1 = ca.y1;
-  va.y2 = ca.y2;
-  va.r1 = ca.r1;
-  va.r2 = ca.r2;
-  va.s = ca.s;
-  va.c = ca.c_out;
-  va.status = status;
-  va.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
-  if (!ctx->gs->full) {  // a light set: variable-base generators (ensure_generators, n <= var_base_max)
-    if ((int64_t)n > var_base_max(ctx)) return fail(CPZ_EINVAL, "internal: variable-base call above var_base_max");
-    va.comb = nullptr;
-    va.vtab = static_cast<const cpz::ge_niels*>(ctx->gs->tab.p);
-    va.vtab16 = static_cast<const int32_t*>(ctx->gs->tab16.p);
-  }
-  va.scratch = nullptr;  // set per launch
-  va.eq_only = ca.eq_only;
+  if (int rc = pair_verify_args(ctx, (int64_t)n, rows, c_buf, status, va)) return rc;
   StageTimer span(ctx, 5, st);  // all chunks, all streams (the launches overlap)
   return launch_verify_chunks(ctx, va, 1, st, rr, join, &ca);
 }
 
-// Stage host inputs on the device.  Returns device pointers through out[].
+// Stage host inputs on the device.  Returns their device views through `out`.
 // Host-buffer calls of up to kPinStageMax input bytes: the rows (and transcript contexts) are
 // packed into page-locked memory and sent with one copy.  A BatchVerifier-sized call made five
 // to eight pageable copies, ~10 us of host round trip each (rocprofv3 timeline, n = 10).
@@ -739,11 +859,17 @@ inline size_t pad16(size_t x) { return (x + 15) & ~size_t(15); }
 // direct (a small synchronous call, zero_copy()): the kernels read the page-locked block
 // itself through its device view -- no copy on the stream -- and *status_dev / *status_host
 // point at n status bytes after it, which the kernels write the same way.
+struct Staged {
+  Rows rows;  // the first `count` of them
+  Ctxs cx;    // offsets relative to the staged blob
+};
+
 int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count, const uint8_t* ctx_bytes,
-                 const uint64_t* ctx_off, const uint8_t* ctx_present, const void* dev[5], const void** dcb,
-                 const uint64_t** dco, const uint8_t** dcp, bool direct = false, uint8_t** status_dev = nullptr,
-                 uint8_t** status_host = nullptr, const void* extra = nullptr, size_t extra_bytes = 0,
-                 const void** dextra = nullptr) {
+                 const uint64_t* ctx_off, const uint8_t* ctx_present, Staged& out, bool direct = false,
+                 uint8_t** status_dev = nullptr, uint8_t** status_host = nullptr, const void* extra = nullptr,
+                 size_t extra_bytes = 0, const void** dextra = nullptr) {
+  const void* dev[5] = {};
+  out = Staged{};
   if (status_dev) *status_dev = nullptr;
   if (ctx_off)
     for (size_t i = 0; i < n; i++)
@@ -784,9 +910,9 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
       CPZ_HIP(hipMemcpyAsync(ctx->in_all.p, h, total, hipMemcpyHostToDevice, ctx->stream));
     }
     for (int k = 0; k < count; k++) dev[k] = d + (size_t)k * n * 32;
-    *dcb = ctx_off ? d + o_ctx : nullptr;
-    *dco = ctx_off ? reinterpret_cast<const uint64_t*>(d + o_off) : nullptr;
-    *dcp = ctx_off && ctx_present ? d + o_pres : nullptr;
+    out.rows = Rows(dev[0], dev[1], dev[2], dev[3], dev[4]);
+    if (ctx_off)
+      out.cx = Ctxs(d + o_ctx, reinterpret_cast<const uint64_t*>(d + o_off), ctx_present ? d + o_pres : nullptr);
     return CPZ_OK;
   }
   (void)hipGetLastError();
@@ -795,9 +921,7 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
     CPZ_HIP(hipMemcpyAsync(ctx->in[k].p, host[k], n * 32, hipMemcpyHostToDevice, ctx->stream));
     dev[k] = ctx->in[k].p;
   }
-  *dcb = nullptr;
-  *dco = nullptr;
-  *dcp = nullptr;
+  out.rows = Rows(dev[0], dev[1], dev[2], dev[3], dev[4]);
   if (extra_bytes) {
     CPZ_HIP(ctx->in[5].ensure(extra_bytes));
     CPZ_HIP(hipMemcpyAsync(ctx->in[5].p, extra, extra_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -814,12 +938,11 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
     CPZ_HIP(hipMemcpyAsync(ctx->ctxo.p, rel.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     // The copies above read pageable host memory synchronously, so rel may be freed.
     CPZ_HIP(hipStreamSynchronize(ctx->stream));
-    *dcb = ctx->ctxb.p;
-    *dco = static_cast<const uint64_t*>(ctx->ctxo.p);
+    out.cx = Ctxs(ctx->ctxb.p, static_cast<const uint64_t*>(ctx->ctxo.p), nullptr);
     if (ctx_present) {
       CPZ_HIP(ctx->ctxp.ensure(n));
       CPZ_HIP(hipMemcpyAsync(ctx->ctxp.p, ctx_present, n, hipMemcpyHostToDevice, ctx->stream));
-      *dcp = static_cast<const uint8_t*>(ctx->ctxp.p);
+      out.cx.present = static_cast<const uint8_t*>(ctx->ctxp.p);
     }
   }
   return CPZ_OK;
@@ -1032,25 +1155,9 @@ int rlc_range(cpz_ctx* ctx, int64_t lo, int64_t hi, hipStream_t st, uint8_t part
 }
 
 // Challenges of the whole batch into ctx->c, response statuses into `status`.
-int batch_challenges(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, const void* r1, const void* r2,
-                     const void* s, const void* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present,
-                     uint8_t* status, hipStream_t st) {
+int batch_challenges(cpz_ctx* ctx, size_t n, const Rows& rows, const Ctxs& cx, uint8_t* status, hipStream_t st) {
   CPZ_HIP(ctx->c.ensure(n * 32));
-  cpz::ChallengeArgs ca;
-  set_challenge_schedules(ctx, ca);
-  ca.n = (int64_t)n;
-  words_from_bytes(ca.gh_words, ctx->gs->gh, ctx->gs->gh + 32);
-  ca.y1 = static_cast<const uint32_t*>(y1);
-  ca.y2 = static_cast<const uint32_t*>(y2);
-  ca.r1 = static_cast<const uint32_t*>(r1);
-  ca.r2 = static_cast<const uint32_t*>(r2);
-  ca.s = static_cast<const uint32_t*>(s);
-  ca.ctx_bytes = static_cast<const uint8_t*>(ctx_bytes);
-  ca.ctx_off = ctx_off;
-  ca.ctx_present = ctx_present;
-  ca.prefix = static_cast<const cpz::StrobeSnap*>(ctx->gs->prefix.p);
-  ca.c_out = static_cast<uint32_t*>(ctx->c.p);
-  ca.status_out = status;
+  const cpz::ChallengeArgs ca = challenge_args(ctx, (int64_t)n, rows, cx, static_cast<uint32_t*>(ctx->c.p), status);
   StageTimer t(ctx, 0, st);
   CPZ_HIP(cpz::launch_challenge(ca, st));
   return CPZ_OK;
@@ -1061,9 +1168,8 @@ int batch_challenges(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, con
 // pair_room > 0 (a mixed-pair batch, challenges from k_challenge_pairs): both sets are reserved
 // for that many proofs more -- the room of the pairs' extra points -- and the prepare writes every
 // proof's products a s and b s (RlcPrepared::prod) instead of the block sums.
-int rlc_prepare_points(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, const void* r1, const void* r2,
-                       const void* s, uint8_t* status, const uint8_t seed[32], uint64_t first_index, hipStream_t st,
-                       bool need_msm = true, int64_t pair_room = 0) {
+int rlc_prepare_points(cpz_ctx* ctx, size_t n, const Rows& rows, uint8_t* status, const uint8_t seed[32],
+                       uint64_t first_index, hipStream_t st, bool need_msm = true, int64_t pair_room = 0) {
   int rc = need_msm ? rlc_reserve(ctx, (int64_t)n + pair_room) : rlc_reserve_prepared(ctx->rl_prep, (int64_t)n);
   if (rc) return rc;
   if (pair_room) CPZ_HIP(ctx->rl_prep.prod.ensure((size_t)ctx->rl_prep.cap * 2 * sizeof(cpz::sc)));
@@ -1072,11 +1178,7 @@ int rlc_prepare_points(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, c
   pa.n = (int64_t)n;
   pa.first_index = first_index;
   std::memcpy(pa.seed, seed, 32);
-  pa.y1 = static_cast<const uint32_t*>(y1);
-  pa.y2 = static_cast<const uint32_t*>(y2);
-  pa.r1 = static_cast<const uint32_t*>(r1);
-  pa.r2 = static_cast<const uint32_t*>(r2);
-  pa.s = static_cast<const uint32_t*>(s);
+  set_rows(pa, rows);
   pa.c = static_cast<const uint32_t*>(ctx->c.p);
   pa.status = status;
   pa.pts = static_cast<cpz::ge_niels*>(ctx->rl_prep.pts.p);
@@ -1101,73 +1203,98 @@ int rlc_prepare_points(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, c
   return CPZ_OK;
 }
 
-// Prepare (challenge + decode + weights + points/digits) for the whole batch.
-int rlc_prepare(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, const void* r1, const void* r2,
-                const void* s, const void* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present,
-                uint8_t* status, const uint8_t seed[32], uint64_t first_index, hipStream_t st) {
-  int rc = batch_challenges(ctx, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present, status, st);
-  if (rc) return rc;
-  return rlc_prepare_points(ctx, n, y1, y2, r1, r2, s, status, seed, first_index, st);
-}
-
 // Batch-fail fallback by bisection (verify_individually, batch.rs:262-268, 314-318): locate
 // the invalid entries of [lo, hi) exactly, for batches the density probe found sparse (or too
 // small to sample, below kProbeMin).  The range is cut in kFanout parts aligned to the weight
 // blocks, each part's partial is one more MSM over the prepared points, identity parts are
-// accepted, failing parts recurse; a range is verified per proof (k_verify_prepared: the
-// prepare's decoded points, challenges and decode-level statuses, the equations only) when it
-// is <= kLeaf or when most of its parts fail.
+// accepted, failing parts recurse; a range is verified per proof when it is a leaf of its route
+// or when most of its parts fail.
 constexpr int64_t kLeaf = 1 << 16;
 constexpr int kFanout = 8;
+constexpr int kBisectMaxDepth = 12;
 constexpr int64_t kProbeMin = 1 << 20;
 using cpz::kProbeChunks;
 
-int rlc_fallback(cpz_ctx* ctx, int64_t lo, int64_t hi, const void* y1, const void* y2, const void* r1, const void* r2,
-                 const void* s, uint8_t* status, hipStream_t st, int depth) {
-  auto per_proof = [&](int64_t a, int64_t b) -> int {
-    ctx->fb_stats[4] += (uint64_t)(b - a);
-    cpz::VerifyArgs va;
-    va.n = b - a;
-    va.y1 = static_cast<const uint32_t*>(y1) + 8 * a;
-    va.y2 = static_cast<const uint32_t*>(y2) + 8 * a;
-    va.r1 = static_cast<const uint32_t*>(r1) + 8 * a;
-    va.r2 = static_cast<const uint32_t*>(r2) + 8 * a;
-    va.s = static_cast<const uint32_t*>(s) + 8 * a;
-    va.c = static_cast<const uint32_t*>(ctx->c.p) + 8 * a;
-    va.status = status + a;  // decode-level status in, final status out
-    va.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
-    va.scratch = nullptr;  // set per launch
-    va.eq_only = ctx->call_eq ? 1 : 0;
-    va.pre = static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p) + 4 * a;
-    return launch_verify_chunks(ctx, va, 4, st, nullptr, true);
-  };
-  if (hi - lo <= kLeaf || depth > 12) return per_proof(lo, hi);
-  int64_t cuts[kFanout + 1];
+// The parts of [lo, hi) (lo a multiple of the weight block): cuts[k] .. cuts[k + 1], some empty.
+// block_parts: a range of at most kFanout weight blocks gets a part per block, so that a range
+// just above one block is still cut.
+void bisect_cuts(int64_t lo, int64_t hi, bool block_parts, int64_t cuts[kFanout + 1]) {
   for (int k = 0; k <= kFanout; k++) {
     int64_t c = lo + ((hi - lo) * k) / kFanout;
     c = (c / cpz::kRlcPrepBlock) * cpz::kRlcPrepBlock;
     cuts[k] = k == 0 ? lo : (k == kFanout ? hi : (c < lo ? lo : c));
   }
-  bool fail[kFanout];
+  if (block_parts && hi - lo <= (int64_t)kFanout * cpz::kRlcPrepBlock)
+    for (int k = 1; k <= kFanout; k++) cuts[k] = std::min<int64_t>(lo + (int64_t)k * cpz::kRlcPrepBlock, hi);
+}
+
+// What a route through the bisection supplies (RlcRoute, PairsRoute, ManyRoute):
+//   kBlockParts                          bisect_cuts' block_parts
+//   bool leaf(lo, hi)                    [lo, hi) is verified per proof without another cut
+//   int part_identity(a, b, int* ident)  the MSM over [a, b), its identity flag read back
+//   int per_proof(lo, hi)                per-proof verification of [lo, hi): a leaf, or a dense range
+//   int part_failed(lo, hi, nfail)       after the nfail-th failing part of [lo, hi)
+//   int parts_done(lo, hi, dense, bool* taken)   before the dense decision; *taken: the route has
+//                                        dealt with the whole range itself
+// BisectRoute has the last two for a route that does nothing there.
+struct BisectRoute {
+  static constexpr bool kBlockParts = false;
+  int part_failed(int64_t, int64_t, int) { return CPZ_OK; }
+  int parts_done(int64_t, int64_t, bool, bool*) { return CPZ_OK; }
+};
+
+template <class Route>
+int bisect(cpz_ctx* ctx, Route& r, int64_t lo, int64_t hi, int depth) {
+  if (depth > kBisectMaxDepth || r.leaf(lo, hi)) return r.per_proof(lo, hi);
+  int64_t cuts[kFanout + 1];
+  bisect_cuts(lo, hi, Route::kBlockParts, cuts);
+  bool failing[kFanout];
   int nfail = 0;
   for (int k = 0; k < kFanout; k++) {
-    fail[k] = false;
+    failing[k] = false;
     if (cuts[k + 1] <= cuts[k]) continue;
-    uint8_t part[32];
     int ident = 0;
-    int rc = rlc_range(ctx, cuts[k], cuts[k + 1], st, part, &ident);
-    if (rc) return rc;
+    if (int rc = r.part_identity(cuts[k], cuts[k + 1], &ident)) return rc;
     ctx->fb_stats[5] += 1;
-    fail[k] = !ident;
-    nfail += fail[k] ? 1 : 0;
+    if (ident) continue;
+    failing[k] = true;
+    if (int rc = r.part_failed(lo, hi, ++nfail)) return rc;
   }
-  if (2 * nfail > kFanout) return per_proof(lo, hi);  // dense failures: no pruning left
+  const bool dense = 2 * nfail > kFanout;  // dense failures: no pruning left
+  bool taken = false;
+  if (int rc = r.parts_done(lo, hi, dense, &taken)) return rc;
+  if (taken) return CPZ_OK;
+  if (dense) return r.per_proof(lo, hi);
   for (int k = 0; k < kFanout; k++) {
-    if (!fail[k]) continue;
-    int rc = rlc_fallback(ctx, cuts[k], cuts[k + 1], y1, y2, r1, r2, s, status, st, depth + 1);
-    if (rc) return rc;
+    if (!failing[k]) continue;
+    if (int rc = bisect(ctx, r, cuts[k], cuts[k + 1], depth + 1)) return rc;
   }
   return CPZ_OK;
+}
+
+// The default pair's route: leaves of kLeaf proofs, verified by k_verify_prepared (the prepare's
+// decoded points, challenges and decode-level statuses, the equations only).
+struct RlcRoute : BisectRoute {
+  cpz_ctx* ctx;
+  cpz::VerifyArgs batch;  // batch_verify_args of the whole batch: decode-level status in, final status out
+  hipStream_t st;
+  bool leaf(int64_t lo, int64_t hi) const { return hi - lo <= kLeaf; }
+  int part_identity(int64_t a, int64_t b, int* ident) {
+    uint8_t part[32];
+    return rlc_range(ctx, a, b, st, part, ident);
+  }
+  int per_proof(int64_t a, int64_t b) {
+    ctx->fb_stats[4] += (uint64_t)(b - a);
+    return launch_verify_chunks(ctx, verify_args_at(batch, a, b - a), 4, st, nullptr, true);
+  }
+};
+
+int rlc_fallback(cpz_ctx* ctx, int64_t n, int64_t lo, int64_t hi, const Rows& rows, uint8_t* status, hipStream_t st) {
+  RlcRoute r;
+  r.ctx = ctx;
+  r.batch = batch_verify_args(ctx, n, rows, status);
+  r.st = st;
+  return bisect(ctx, r, lo, hi, 0);
 }
 
 // The density probe of a fallback-enabled batch check, launched BEFORE the prepare on its own
@@ -1177,8 +1304,8 @@ int rlc_fallback(cpz_ctx* ctx, int64_t lo, int64_t hi, const void* y1, const voi
 // own context blob (the challenge kernel reads them through ChallengeArgs::ctx_end), so
 // batches with contexts (the service's, service.rs:512-517) are sampled the same way.
 // Returns the number of chunk starts.
-int launch_probe(cpz_ctx* ctx, size_t n, const void* const rows[5], const void* cb, const uint64_t* co,
-                 const uint8_t* cp, int64_t starts[kProbeChunks], hipStream_t st) {
+int launch_probe(cpz_ctx* ctx, size_t n, const Rows& rows, const Ctxs& cx, int64_t starts[kProbeChunks],
+                 hipStream_t st) {
   const int64_t blk = cpz::kRlcPrepBlock;
   const size_t m = (size_t)kProbeChunks * blk;
   // rows (5 x 32 B), challenges (32 B), statuses (1 B), then context begin / end (2 x 8 B) and
@@ -1186,30 +1313,31 @@ int launch_probe(cpz_ctx* ctx, size_t n, const void* const rows[5], const void* 
   CPZ_HIP(ctx->probe.ensure(m * (5 * 32 + 32 + 1 + 16 + 1) + 16));
   if (!ctx->probe_stream) CPZ_HIP(stream_own_queue(&ctx->probe_stream, ctx->cus, ctx->device, &ctx->own_queues));
   if (!ctx->probe_done) CPZ_HIP(hipEventCreateWithFlags(&ctx->probe_done, hipEventDisableTiming));
-  if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
-  CPZ_HIP(hipEventRecord(ctx->aux_start, st));  // after everything before this call on st
+  if (int rc = fork_verify_streams(ctx, st, 1)) return rc;  // aux_start: after everything before this call on st
   CPZ_HIP(hipStreamWaitEvent(ctx->probe_stream, ctx->aux_start, 0));
   uint8_t* base = static_cast<uint8_t*>(ctx->probe.p);
   cpz::ProbeGatherArgs ga;
   const int64_t span = (int64_t)n / kProbeChunks;
   for (int k = 0; k < kProbeChunks; k++) ga.starts[k] = starts[k] = ((k * span + span / 2) / blk) * blk;
   ga.blk = (int)blk;
+  const uint32_t* const in[5] = {rows.y1, rows.y2, rows.r1, rows.r2, rows.s};
   for (int q = 0; q < 5; q++) {
-    ga.rows[q] = static_cast<const uint32_t*>(rows[q]);
+    ga.rows[q] = in[q];
     ga.out_rows[q] = reinterpret_cast<uint32_t*>(base + q * m * 32);
   }
   uint32_t* pc = reinterpret_cast<uint32_t*>(base + 5 * m * 32);
   uint8_t* pst = base + 6 * m * 32;
   uint64_t* pbeg = reinterpret_cast<uint64_t*>(base + ((6 * m * 32 + m + 15) & ~(size_t)15));
-  ga.ctx_off = co;
-  ga.ctx_present = cp;
+  ga.ctx_off = cx.off;
+  ga.ctx_present = cx.present;
   ga.out_begin = pbeg;
   ga.out_end = pbeg + m;
   ga.out_present = reinterpret_cast<uint8_t*>(pbeg + 2 * m);
   CPZ_HIP(cpz::launch_probe_gather(ga, ctx->probe_stream));
-  int rc = enqueue_verify(ctx, m, ga.out_rows[0], ga.out_rows[1], ga.out_rows[2], ga.out_rows[3], ga.out_rows[4],
-                          co ? cb : nullptr, co ? ga.out_begin : nullptr, co ? ga.out_present : nullptr, pst,
-                          ctx->probe_stream, pc, nullptr, true, co ? ga.out_end : nullptr);
+  const Rows sampled(ga.out_rows[0], ga.out_rows[1], ga.out_rows[2], ga.out_rows[3], ga.out_rows[4]);
+  const Ctxs sampled_cx = cx.off ? Ctxs(cx.bytes, ga.out_begin, ga.out_present) : Ctxs();
+  int rc = enqueue_verify(ctx, m, sampled, sampled_cx, pst, ctx->probe_stream, pc, nullptr, true,
+                          cx.off ? ga.out_end : nullptr);
   if (rc) return rc;
   CPZ_HIP(hipEventRecord(ctx->probe_done, ctx->probe_stream));
   return kProbeChunks;
@@ -1219,7 +1347,7 @@ int launch_probe(cpz_ctx* ctx, size_t n, const void* const rows[5], const void* 
 // each) of the prepared batch: a workgroup takes kVerifyBlock / kPartProofs consecutive listed
 // blocks; launches of at most half the occupancy grid, round-robin over the verify streams and
 // their scratch slabs (as launch_verify_chunks).
-int verify_prepared_blocks(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* status, const uint32_t* d_blocks,
+int verify_prepared_blocks(cpz_ctx* ctx, int64_t n, const uint32_t* s, uint8_t* status, const uint32_t* d_blocks,
                            int64_t nb, int block_proofs, hipStream_t st) {
   if (block_proofs <= 0 || cpz::kVerifyBlock % block_proofs != 0) return CPZ_EINVAL;
   const int64_t G = cpz::kVerifyBlock / block_proofs;
@@ -1228,45 +1356,22 @@ int verify_prepared_blocks(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* stat
   const size_t slab = verify_slab_bytes(ctx);
   CPZ_HIP(ctx->scratch.ensure((size_t)CPZ_VERIFY_STREAMS * slab));
   const int64_t quad_max = verify_quad_max(ctx);
+  cpz::VerifyArgs va = batch_verify_args(ctx, n, Rows(nullptr, nullptr, nullptr, nullptr, s), status);
+  va.block_proofs = block_proofs;
   if (CPZ_VERIFY_QUAD && nb * block_proofs <= quad_max) {  // one eight-lanes-per-proof launch (k_verify_quad)
-    cpz::VerifyArgs v;
-    v.n = n;
-    v.s = static_cast<const uint32_t*>(s);
-    v.c = static_cast<const uint32_t*>(ctx->c.p);
-    v.status = status;
-    v.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
-    v.pre = static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p);
-    v.eq_only = ctx->call_eq ? 1 : 0;
-    v.scratch = static_cast<char*>(ctx->scratch.p);
-    v.blocks = d_blocks;
-    v.block_proofs = block_proofs;
-    v.nblocks = nb;
-    v.quad_max = quad_max;
+    va.scratch = static_cast<char*>(ctx->scratch.p);
+    va.blocks = d_blocks;
+    va.nblocks = nb;
+    va.quad_max = quad_max;
     StageTimer t(ctx, 1, st);
-    CPZ_HIP(cpz::launch_verify_each(v, 0, st));
+    CPZ_HIP(cpz::launch_verify_each(va, 0, st));
     return CPZ_OK;
   }
   const int64_t groups = (nb + G - 1) / G;
   const int64_t chunks = (groups + full - 1) / full;
   const int nst = (int)std::min<int64_t>(CPZ_VERIFY_STREAMS, chunks);
-  if (nst > 1) {
-    if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
-    CPZ_HIP(hipEventRecord(ctx->aux_start, st));
-    for (int k = 0; k < nst - 1; k++) {
-      if (!ctx->aux_stream[k]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[k], ctx->cus, ctx->device, &ctx->own_queues));
-      if (!ctx->aux_done[k]) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_done[k], hipEventDisableTiming));
-      CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->aux_start, 0));
-    }
-  }
-  cpz::VerifyArgs va;
-  va.n = n;
-  va.s = static_cast<const uint32_t*>(s);
-  va.c = static_cast<const uint32_t*>(ctx->c.p);
-  va.status = status;
-  va.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
-  va.pre = static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p);
-  va.eq_only = ctx->call_eq ? 1 : 0;
-  va.block_proofs = block_proofs;
+  if (nst > 1)
+    if (int rc = fork_verify_streams(ctx, st, nst)) return rc;
   for (int64_t c = 0; c < chunks; c++) {
     const int64_t g0 = c * full;
     const int g = (int)std::min<int64_t>(full, groups - g0);
@@ -1279,12 +1384,7 @@ int verify_prepared_blocks(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* stat
     StageTimer t(ctx, 1, sc);
     CPZ_HIP(cpz::launch_verify_each(v, g, sc));
   }
-  if (nst > 1) {
-    for (int k = 0; k < nst - 1; k++) {
-      CPZ_HIP(hipEventRecord(ctx->aux_done[k], ctx->aux_stream[k]));
-      CPZ_HIP(hipStreamWaitEvent(st, ctx->aux_done[k], 0));
-    }
-  }
+  if (nst > 1) return join_verify_streams(ctx, st, nst);
   return CPZ_OK;
 }
 
@@ -1361,7 +1461,7 @@ struct PartPairs {
   int npairs;
 };
 
-int part_locate(cpz_ctx* ctx, int64_t n, const void* s, const uint8_t* d_status, const uint8_t seed[32],
+int part_locate(cpz_ctx* ctx, int64_t n, const uint32_t* s, const uint8_t* d_status, const uint8_t seed[32],
                 uint64_t first_index, const std::vector<uint32_t>& blocks, std::vector<uint32_t>& whole,
                 std::vector<uint32_t>& cand, hipStream_t st, const PartPairs* px = nullptr) {
   const int64_t nf = (int64_t)blocks.size();
@@ -1384,7 +1484,7 @@ int part_locate(cpz_ctx* ctx, int64_t n, const void* s, const uint8_t* d_status,
     ia.blocks = d_blocks;
     ia.first_index = first_index;
     std::memcpy(ia.seed, seed, 32);
-    ia.s = static_cast<const uint32_t*>(s);
+    ia.s = s;
     ia.c = px ? px->c : static_cast<const uint32_t*>(ctx->c.p);
     ia.status = d_status;
     ia.digits = static_cast<int16_t*>(ctx->pt_ldig.p);
@@ -1451,30 +1551,51 @@ int part_locate(cpz_ctx* ctx, int64_t n, const void* s, const uint8_t* d_status,
   return CPZ_OK;
 }
 
-// Per-proof verification (k_verify_prepared) of the located proofs alone and of the `whole`
-// blocks.  A located proof that verifies (a 2^-121 event: the locate pass accepted its block's
-// other proofs on P'_b = [j] P_b) sends its block to per-proof verification as well.
-int part_verify_lists(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* d_status, const std::vector<uint32_t>& blocks,
-                      std::vector<uint32_t> whole, const std::vector<uint32_t>& cand, hipStream_t st) {
-  uint32_t* d_list = static_cast<uint32_t*>(ctx->pt_blocks.p) + blocks.size();  // after the failing blocks
+// The failing blocks among the nblk whose flags the block pass left in pt_fail (synchronises
+// `st`), counted into the stats.
+int part_failing_blocks(cpz_ctx* ctx, int64_t nblk, std::vector<uint32_t>& blocks, hipStream_t st) {
+  std::vector<uint8_t> dirty((size_t)nblk);
+  CPZ_HIP(hipMemcpyAsync(dirty.data(), ctx->pt_fail.p, (size_t)nblk, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  for (int64_t b = 0; b < nblk; b++)
+    if (dirty[(size_t)b]) blocks.push_back((uint32_t)b);
+  ctx->fb_stats[2] += (uint64_t)nblk;  // (zero before a call's first pass)
+  ctx->fb_stats[3] += blocks.size();
+  return CPZ_OK;
+}
+
+// Per-proof verification of the located proofs alone and of the `whole` blocks of a range of n
+// proofs that starts at entry lo of its batch (a multiple of kPartProofs; `cand` and `whole` count
+// from lo).  verify_listed(d_list, count, block_proofs) verifies listed blocks of the batch:
+// verify_prepared_blocks, or pairs_verify_listed for a mixed-pair batch.  A located proof that
+// verifies (a 2^-121 event: the locate pass accepted its block's other proofs on P'_b = [j] P_b)
+// sends its block to per-proof verification as well.
+template <class VerifyListed>
+int part_verify_lists(cpz_ctx* ctx, int64_t n, int64_t lo, const uint8_t* d_status, size_t nfailing,
+                      std::vector<uint32_t> whole, std::vector<uint32_t> cand, hipStream_t st,
+                      VerifyListed verify_listed) {
+  uint32_t* d_list = static_cast<uint32_t*>(ctx->pt_blocks.p) + nfailing;  // after the failing blocks
   StageTimer span(ctx, 4, st);  // wall time of the per-proof pass; launches timed as verify_each
   if (!cand.empty()) {
     ctx->fb_stats[4] += (uint64_t)cand.size();
+    for (uint32_t& e : cand) e += (uint32_t)lo;
     CPZ_HIP(hipMemcpyAsync(d_list, cand.data(), cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (int rc = verify_prepared_blocks(ctx, n, s, d_status, d_list, (int64_t)cand.size(), 1, st)) return rc;
+    if (int rc = verify_listed(d_list, (int64_t)cand.size(), 1)) return rc;
     std::vector<uint8_t> cst(cand.size());
     uint8_t* d_cst = static_cast<uint8_t*>(ctx->pt_lfail.p);  // |cand| <= failing blocks bytes, spent
     CPZ_HIP(cpz::launch_gather_status(d_status, d_list, (int64_t)cand.size(), d_cst, st));
     CPZ_HIP(hipMemcpyAsync(cst.data(), d_cst, cand.size(), hipMemcpyDeviceToHost, st));
     CPZ_HIP(hipStreamSynchronize(st));
     for (size_t k = 0; k < cand.size(); k++)
-      if (cst[k] == cpz::kStatusOk) whole.push_back(cand[k] / (uint32_t)cpz::kPartProofs);
+      if (cst[k] == cpz::kStatusOk) whole.push_back((cand[k] - (uint32_t)lo) / (uint32_t)cpz::kPartProofs);
   }
   if (whole.empty()) return CPZ_OK;
-  for (uint32_t b : whole) ctx->fb_stats[4] += (uint64_t)std::min<int64_t>(cpz::kPartProofs, n - (int64_t)b * cpz::kPartProofs);
+  for (uint32_t& b : whole) {
+    ctx->fb_stats[4] += (uint64_t)std::min<int64_t>(cpz::kPartProofs, n - (int64_t)b * cpz::kPartProofs);
+    b += (uint32_t)(lo / cpz::kPartProofs);
+  }
   CPZ_HIP(hipMemcpyAsync(d_list, whole.data(), whole.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (int rc = verify_prepared_blocks(ctx, n, s, d_status, d_list, (int64_t)whole.size(), cpz::kPartProofs, st))
-    return rc;
+  if (int rc = verify_listed(d_list, (int64_t)whole.size(), cpz::kPartProofs)) return rc;
   CPZ_HIP(hipStreamSynchronize(st));  // the host lists are pageable memory read by the copies above
   return CPZ_OK;
 }
@@ -1482,7 +1603,7 @@ int part_verify_lists(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* d_status,
 // The partitioned fallback over the prepared batch (buffers from part_reserve): every block's
 // partial (k_part_*), the batch partial as their sum, and per-proof verification of the
 // failing blocks only.
-int part_fallback(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* d_status, const uint8_t seed[32],
+int part_fallback(cpz_ctx* ctx, int64_t n, const uint32_t* s, uint8_t* d_status, const uint8_t seed[32],
                   uint64_t first_index, uint8_t partial[32], int* identity, hipStream_t st) {
   const int64_t nblk = (n + cpz::kPartProofs - 1) / cpz::kPartProofs;
   const int64_t chunk = std::min<int64_t>(nblk, kPartChunkBlocks);
@@ -1523,18 +1644,11 @@ int part_fallback(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* d_status, con
                                  static_cast<uint32_t*>(ctx->rl_msm.partial.p), static_cast<int*>(ctx->rl_msm.flags.p),
                                  st));
   }
-  std::vector<uint8_t> dirty((size_t)nblk);
-  int flags[1];
-  CPZ_HIP(hipMemcpyAsync(dirty.data(), ctx->pt_fail.p, (size_t)nblk, hipMemcpyDeviceToHost, st));
+  // the partial and its identity flag come back with the fail flags' synchronisation
   CPZ_HIP(hipMemcpyAsync(partial, ctx->rl_msm.partial.p, 32, hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipMemcpyAsync(flags, ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipStreamSynchronize(st));
-  *identity = flags[0];
+  CPZ_HIP(hipMemcpyAsync(identity, ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
   std::vector<uint32_t> blocks;
-  for (int64_t b = 0; b < nblk; b++)
-    if (dirty[(size_t)b]) blocks.push_back((uint32_t)b);
-  ctx->fb_stats[2] = (uint64_t)nblk;
-  ctx->fb_stats[3] = blocks.size();
+  if (int rc = part_failing_blocks(ctx, nblk, blocks, st)) return rc;
   if (blocks.empty()) return CPZ_OK;
   CPZ_HIP(hipMemcpyAsync(ctx->pt_blocks.p, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   std::vector<uint32_t> whole = blocks;  // blocks verified per proof
@@ -1545,11 +1659,24 @@ int part_fallback(cpz_ctx* ctx, int64_t n, const void* s, uint8_t* d_status, con
     int rc = part_locate(ctx, n, s, d_status, seed, first_index, blocks, whole, cand, st);
     if (rc) return rc;
   }
-  return part_verify_lists(ctx, n, s, d_status, blocks, whole, cand, st);
+  return part_verify_lists(ctx, n, 0, d_status, blocks.size(), whole, cand, st,
+                           [&](const uint32_t* d_list, int64_t nb, int block_proofs) {
+                             return verify_prepared_blocks(ctx, n, s, d_status, d_list, nb, block_proofs, st);
+                           });
 }
 
-int verify_batch_impl(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, const void* r1, const void* r2,
-                      const void* s, const void* cb, const uint64_t* co, const uint8_t* cp, uint8_t* d_status,
+// The statuses of a finished search complete on `st` on return (documented), and copied to the
+// host buffer of a host-buffer call.
+int finish_statuses(size_t n, const uint8_t* d_status, uint8_t* host_status, hipStream_t st) {
+  CPZ_HIP(hipStreamSynchronize(st));
+  if (host_status) {
+    CPZ_HIP(hipMemcpyAsync(host_status, d_status, n, hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+  }
+  return CPZ_OK;
+}
+
+int verify_batch_impl(cpz_ctx* ctx, size_t n, const Rows& rows, const Ctxs& cx, uint8_t* d_status,
                       const uint8_t seed[32], uint64_t first_index, uint8_t partial_out[32], int* batch_ok,
                       int fallback, uint8_t* host_status, hipStream_t st) {
   // A fallback-enabled check of a large batch (with or without contexts) first samples its
@@ -1567,12 +1694,12 @@ int verify_batch_impl(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, co
   int64_t starts[kProbeChunks];
   const bool probe = fallback && (int64_t)n >= kProbeMin;
   if (probe) {
-    const void* rows[5] = {y1, y2, r1, r2, s};
-    int rc = launch_probe(ctx, n, rows, cb, co, cp, starts, st);
+    int rc = launch_probe(ctx, n, rows, cx, starts, st);
     if (rc < 0) return rc;
   }
-  int rc = batch_challenges(ctx, n, y1, y2, r1, r2, s, cb, co, cp, d_status, st);
+  int rc = batch_challenges(ctx, n, rows, cx, d_status, st);
   if (rc) return rc;
+  int bad = 0;  // invalid entries among the sampled
   if (probe) {
     const size_t m = (size_t)kProbeChunks * cpz::kRlcPrepBlock;
     std::vector<uint8_t> pst(m);
@@ -1580,7 +1707,6 @@ int verify_batch_impl(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, co
     CPZ_HIP(hipMemcpyAsync(pst.data(), static_cast<uint8_t*>(ctx->probe.p) + 6 * m * 32, m, hipMemcpyDeviceToHost,
                            ctx->probe_stream));
     CPZ_HIP(hipStreamSynchronize(ctx->probe_stream));
-    int bad = 0;
     for (uint8_t v : pst) bad += (v == cpz::kStatusEqFail) ? 1 : 0;
     ctx->fb_stats[1] = (uint64_t)bad;
     // The partitioned check's buffers (the prepared batch, ~40 KB of window sums per block,
@@ -1590,50 +1716,34 @@ int verify_batch_impl(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, co
       part_release(ctx);
       bad = kPartMaxProbeBad + 1;
     }
-    if (bad >= 2 && bad <= kPartMaxProbeBad) {
-      ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
-      if ((rc = rlc_prepare_points(ctx, n, y1, y2, r1, r2, s, d_status, seed, first_index, st, false))) return rc;
-      uint8_t part[32];
-      int ident = 0;
-      if ((rc = part_fallback(ctx, (int64_t)n, s, d_status, seed, first_index, part, &ident, st))) return rc;
-      if (partial_out) std::memcpy(partial_out, part, 32);
-      if (batch_ok) *batch_ok = 0;  // the probe saw invalid entries
-      if (host_status) {
-        CPZ_HIP(hipMemcpyAsync(host_status, d_status, n, hipMemcpyDeviceToHost, st));
-        CPZ_HIP(hipStreamSynchronize(st));
-      }
-      return CPZ_OK;
-    }
-    if (bad > kPartMaxProbeBad) {
-      ctx->fb_stats[0] = CPZ_FALLBACK_PER_PROOF;
-      ctx->fb_stats[4] = (uint64_t)n;
-      if (partial_out) std::memset(partial_out, 0xff, 32);
-      if (batch_ok) *batch_ok = 0;
-      cpz::VerifyArgs va;
-      va.n = (int64_t)n;
-      va.y1 = static_cast<const uint32_t*>(y1);
-      va.y2 = static_cast<const uint32_t*>(y2);
-      va.r1 = static_cast<const uint32_t*>(r1);
-      va.r2 = static_cast<const uint32_t*>(r2);
-      va.s = static_cast<const uint32_t*>(s);
-      va.c = static_cast<const uint32_t*>(ctx->c.p);
-      va.status = d_status;  // response statuses from batch_challenges -> final statuses
-      va.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
-      va.scratch = nullptr;  // set per launch
-      va.eq_only = ctx->call_eq ? 1 : 0;
-      {
-        StageTimer span(ctx, 4, st);  // wall time of the fallback; launches timed as verify_each
-        if ((rc = launch_verify_chunks(ctx, va, 1, st, nullptr, true))) return rc;
-      }
-      CPZ_HIP(hipStreamSynchronize(st));
-      if (host_status) {
-        CPZ_HIP(hipMemcpyAsync(host_status, d_status, n, hipMemcpyDeviceToHost, st));
-        CPZ_HIP(hipStreamSynchronize(st));
-      }
-      return CPZ_OK;
-    }
   }
-  if ((rc = rlc_prepare_points(ctx, n, y1, y2, r1, r2, s, d_status, seed, first_index, st))) return rc;
+  if (bad >= 2 && bad <= kPartMaxProbeBad) {  // the probe's first outcome: partitioned
+    ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
+    if ((rc = rlc_prepare_points(ctx, n, rows, d_status, seed, first_index, st, false))) return rc;
+    uint8_t part[32];
+    int ident = 0;
+    if ((rc = part_fallback(ctx, (int64_t)n, rows.s, d_status, seed, first_index, part, &ident, st))) return rc;
+    if (partial_out) std::memcpy(partial_out, part, 32);
+    if (batch_ok) *batch_ok = 0;  // the probe saw invalid entries
+    if (host_status) return finish_statuses(n, d_status, host_status, st);
+    return CPZ_OK;
+  }
+  if (bad > kPartMaxProbeBad) {  // its second: per proof, no partial
+    ctx->fb_stats[0] = CPZ_FALLBACK_PER_PROOF;
+    ctx->fb_stats[4] = (uint64_t)n;
+    if (partial_out) std::memset(partial_out, 0xff, 32);
+    if (batch_ok) *batch_ok = 0;
+    // response statuses from batch_challenges -> final statuses
+    cpz::VerifyArgs va = batch_verify_args(ctx, (int64_t)n, rows, d_status);
+    va.pre = nullptr;  // nothing was prepared
+    {
+      StageTimer span(ctx, 4, st);  // wall time of the fallback; launches timed as verify_each
+      if ((rc = launch_verify_chunks(ctx, va, 1, st, nullptr, true))) return rc;
+    }
+    return finish_statuses(n, d_status, host_status, st);
+  }
+  // its third, or no probe: the check itself
+  if ((rc = rlc_prepare_points(ctx, n, rows, d_status, seed, first_index, st))) return rc;
   // The partial, its identity flag, the any-bad word and (host-buffer calls) the statuses come
   // back with one synchronisation, into page-locked memory when it is there: a valid batch
   // needs no second round trip.  A failing one re-reads the statuses after its fallback.
@@ -1657,59 +1767,48 @@ int verify_batch_impl(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, co
   if (partial_out) std::memcpy(partial_out, part, 32);
   const bool all_live = any_bad == 0;
   if (batch_ok) *batch_ok = (ident && all_live) ? 1 : 0;
-  if (!ident && fallback) {
-    // A batch of several MSM spans whose failure lies in at most half of them: each span's own
-    // P was tested by its final (RlcMsmArgs::span_identity), so only the failing spans are
-    // searched, each by bisection over its prepared points (configs[3]'s forged variant: 2 of
-    // 32 spans) -- the partitioned pass below would walk every block of the whole batch.
-    const int64_t nspan = ((int64_t)n + CPZ_RLC_SPAN - 1) / CPZ_RLC_SPAN;
-    if (nspan > 1) {
-      std::vector<int> sid((size_t)nspan);
-      CPZ_HIP(hipMemcpyAsync(sid.data(), ctx->rl_span_ident.p, (size_t)nspan * sizeof(int), hipMemcpyDeviceToHost, st));
-      CPZ_HIP(hipStreamSynchronize(st));
-      int64_t nfail = 0;
-      for (int v : sid) nfail += v ? 0 : 1;
-      if (nfail > 0 && 2 * nfail <= nspan) {
-        part_release_blocks(ctx);
-        ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
-        for (int64_t j = 0; j < nspan; j++) {
-          if (sid[(size_t)j]) continue;
-          const int64_t slo = j * CPZ_RLC_SPAN, shi = std::min<int64_t>((int64_t)n, slo + CPZ_RLC_SPAN);
-          if ((rc = rlc_fallback(ctx, slo, shi, y1, y2, r1, r2, s, d_status, st, 0))) return rc;
-        }
-        CPZ_HIP(hipStreamSynchronize(st));
-        if (host_status) {
-          CPZ_HIP(hipMemcpyAsync(host_status, d_status, n, hipMemcpyDeviceToHost, st));
-          CPZ_HIP(hipStreamSynchronize(st));
-        }
-        return CPZ_OK;
-      }
-    }
-    // A large batch that failed: every block's partial over the points just prepared, then
-    // the locate pass and per-proof verification of what it leaves (part_fallback) -- at 2^20
-    // cheaper than bisection from one forged entry up (sub-range MSMs of 1/8 of the range, each
-    // with the whole MSM's sort and tails).  Smaller batches, or no room for the block buffers:
-    // bisection.
-    if (CPZ_SPARSE_PARTITIONED && (int64_t)n >= kPartSparseMin && part_reserve(ctx, (int64_t)n) == CPZ_OK) {
-      ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
-      uint8_t part2[32];
-      int ident2 = 0;
-      if ((rc = part_fallback(ctx, (int64_t)n, s, d_status, seed, first_index, part2, &ident2, st))) return rc;
-    } else {
-      part_release_blocks(ctx);
-      ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
-      rc = rlc_fallback(ctx, 0, (int64_t)n, y1, y2, r1, r2, s, d_status, st, 0);
-      if (rc) return rc;
-    }
-    CPZ_HIP(hipStreamSynchronize(st));  // statuses complete on return (documented)
-    if (host_status) {
-      CPZ_HIP(hipMemcpyAsync(host_status, d_status, n, hipMemcpyDeviceToHost, st));
-      CPZ_HIP(hipStreamSynchronize(st));
-    }
+  if (ident || !fallback) {
+    if (host_status && st_stage != host_status) std::memcpy(host_status, st_stage, n);
     return CPZ_OK;
   }
-  if (host_status && st_stage != host_status) std::memcpy(host_status, st_stage, n);
-  return CPZ_OK;
+  // A batch of several MSM spans whose failure lies in at most half of them: each span's own
+  // P was tested by its final (RlcMsmArgs::span_identity), so only the failing spans are
+  // searched, each by bisection over its prepared points (configs[3]'s forged variant: 2 of
+  // 32 spans) -- the partitioned pass below would walk every block of the whole batch.
+  const int64_t nspan = ((int64_t)n + CPZ_RLC_SPAN - 1) / CPZ_RLC_SPAN;
+  if (nspan > 1) {
+    std::vector<int> sid((size_t)nspan);
+    CPZ_HIP(hipMemcpyAsync(sid.data(), ctx->rl_span_ident.p, (size_t)nspan * sizeof(int), hipMemcpyDeviceToHost, st));
+    CPZ_HIP(hipStreamSynchronize(st));
+    int64_t nfail = 0;
+    for (int v : sid) nfail += v ? 0 : 1;
+    if (nfail > 0 && 2 * nfail <= nspan) {
+      part_release_blocks(ctx);
+      ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
+      for (int64_t j = 0; j < nspan; j++) {
+        if (sid[(size_t)j]) continue;
+        const int64_t slo = j * CPZ_RLC_SPAN, shi = std::min<int64_t>((int64_t)n, slo + CPZ_RLC_SPAN);
+        if ((rc = rlc_fallback(ctx, (int64_t)n, slo, shi, rows, d_status, st))) return rc;
+      }
+      return finish_statuses(n, d_status, host_status, st);
+    }
+  }
+  // A large batch that failed: every block's partial over the points just prepared, then
+  // the locate pass and per-proof verification of what it leaves (part_fallback) -- at 2^20
+  // cheaper than bisection from one forged entry up (sub-range MSMs of 1/8 of the range, each
+  // with the whole MSM's sort and tails).  Smaller batches, or no room for the block buffers:
+  // bisection.
+  if (CPZ_SPARSE_PARTITIONED && (int64_t)n >= kPartSparseMin && part_reserve(ctx, (int64_t)n) == CPZ_OK) {
+    ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
+    uint8_t part2[32];
+    int ident2 = 0;
+    if ((rc = part_fallback(ctx, (int64_t)n, rows.s, d_status, seed, first_index, part2, &ident2, st))) return rc;
+  } else {
+    part_release_blocks(ctx);
+    ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
+    if ((rc = rlc_fallback(ctx, (int64_t)n, 0, (int64_t)n, rows, d_status, st))) return rc;
+  }
+  return finish_statuses(n, d_status, host_status, st);
 }
 
 }  // namespace
@@ -1858,16 +1957,12 @@ int cpz_verify_batch_ex(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], const
   if (rc) return rc;
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
   const uint8_t* host[5] = {y1, y2, r1, r2, s};
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
-  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp);
+  Staged in;
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, in);
   if (rc) return rc;
   CPZ_HIP(ctx->st.ensure(n));
-  return verify_batch_impl(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], dcb, dco, dcp,
-                           static_cast<uint8_t*>(ctx->st.p), seed, first_index, partial_out, batch_ok,
-                           status_out != nullptr, status_out, ctx->stream);
+  return verify_batch_impl(ctx, n, in.rows, in.cx, static_cast<uint8_t*>(ctx->st.p), seed, first_index, partial_out,
+                           batch_ok, status_out != nullptr, status_out, ctx->stream);
 }
 
 int cpz_verify_batch_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const void* d_y1,
@@ -1877,16 +1972,16 @@ int cpz_verify_batch_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[3
                             void* d_status_out, int fallback, void* stream) {
   if (!ctx || !g || !h || !seed) return fail(CPZ_EINVAL, "null context, generators or seed");
   if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
-  if (!d_y1 || !d_y2 || !d_r1 || !d_r2 || !d_s || !d_status_out) return fail(CPZ_EINVAL, "null input pointer");
-  if (!aligned16(d_y1) || !aligned16(d_y2) || !aligned16(d_r1) || !aligned16(d_r2) || !aligned16(d_s))
-    return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
+  const Rows rows(d_y1, d_y2, d_r1, d_r2, d_s);
+  if (!rows.complete() || !d_status_out) return fail(CPZ_EINVAL, "null input pointer");
+  if (!rows.aligned()) return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
   CallLock lock(ctx);
   CPZ_HIP(hipSetDevice(ctx->device));
   int rc = ensure_generators(ctx, g, h);
   if (rc) return rc;
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   if ((rc = order_after_last(ctx, st))) return rc;
-  rc = verify_batch_impl(ctx, n, d_y1, d_y2, d_r1, d_r2, d_s, d_ctx_bytes, d_ctx_off, d_ctx_present,
+  rc = verify_batch_impl(ctx, n, rows, Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present),
                          static_cast<uint8_t*>(d_status_out), seed, first_index, partial_out, batch_ok, fallback,
                          nullptr, st);
   if (rc) return rc;
@@ -2196,6 +2291,17 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
 
 namespace {
 
+// The n statuses in ctx->st to the caller, on ctx->stream (synchronises): through the page-locked
+// block when stage_inputs used it (its inputs are spent).
+int read_back_statuses(cpz_ctx* ctx, size_t n, uint8_t* status_out) {
+  const bool pinned = ctx->pin.cap >= kPinMail + pad16(n);
+  uint8_t* dst = pinned ? static_cast<uint8_t*>(ctx->pin.p) + kPinMail : status_out;
+  CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
+  CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  if (pinned) std::memcpy(status_out, dst, n);
+  return CPZ_OK;
+}
+
 // Host-buffer per-proof verification in chunks of kPipeChunk proofs: the five input
 // arrays of chunk j + 1 are copied (pageable H2D, on ctx->copy_stream) while chunk j's
 // challenge + verify kernels run on ctx->stream, which waits on an event recorded after
@@ -2205,11 +2311,8 @@ namespace {
 // relative to the staged blob).  Statuses come back in one D2H copy at the end.
 int verify_each_pipelined(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], const uint8_t* ctx_bytes,
                           const uint64_t* ctx_off, const uint8_t* ctx_present, uint8_t* status_out) {
-  const void* unused[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
-  int rc = stage_inputs(ctx, n, host, 0, ctx_bytes, ctx_off, ctx_present, unused, &dcb, &dco, &dcp);
+  Staged in;  // the contexts alone
+  int rc = stage_inputs(ctx, n, host, 0, ctx_bytes, ctx_off, ctx_present, in);
   if (rc) return rc;
   for (int k = 0; k < 5; k++) CPZ_HIP(ctx->in[k].ensure(n * 32));
   CPZ_HIP(ctx->st.ensure(n));
@@ -2227,8 +2330,7 @@ int verify_each_pipelined(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], 
     }
     CPZ_HIP(hipEventRecord(ctx->copy_done, ctx->copy_stream));
     CPZ_HIP(hipStreamWaitEvent(ctx->stream, ctx->copy_done, 0));
-    rc = enqueue_verify(ctx, m, d[0], d[1], d[2], d[3], d[4], dcb, dco ? dco + off : nullptr,
-                        dcp ? dcp + off : nullptr, st + off, ctx->stream,
+    rc = enqueue_verify(ctx, m, Rows(d[0], d[1], d[2], d[3], d[4]), in.cx.at((int64_t)off), st + off, ctx->stream,
                         static_cast<uint32_t*>(ctx->c.p) + 8 * off, &rr, false);
     if (rc) {
       (void)join_verify_streams(ctx, ctx->stream);
@@ -2245,23 +2347,19 @@ int verify_each_pipelined(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], 
 
 // cpz_verify_each_device with per-call flags (the one-pair case of cpz_verify_each_pairs_device).
 int verify_each_device_flags(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], const uint8_t h[32], size_t n,
-                             const void* d_y1, const void* d_y2, const void* d_r1, const void* d_r2, const void* d_s,
-                             const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
-                             void* d_status_out, void* stream) {
+                             const Rows& rows, const Ctxs& cx, void* d_status_out, void* stream) {
   if (!ctx || !g || !h) return fail(CPZ_EINVAL, "null context or generators");
   if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
-  if (!d_y1 || !d_y2 || !d_r1 || !d_r2 || !d_s || !d_status_out) return fail(CPZ_EINVAL, "null input pointer");
-  if (!aligned16(d_y1) || !aligned16(d_y2) || !aligned16(d_r1) || !aligned16(d_r2) || !aligned16(d_s))
-    return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
-  if (d_ctx_off && !d_ctx_bytes) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  if (!rows.complete() || !d_status_out) return fail(CPZ_EINVAL, "null input pointer");
+  if (!rows.aligned()) return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
+  if (int rc = check_contexts(cx.bytes, cx.off, n, true)) return rc;
   CallLock lock(ctx, flags);
   CPZ_HIP(hipSetDevice(ctx->device));
   int rc = ensure_generators(ctx, g, h, (int64_t)n > var_base_max(ctx));
   if (rc) return rc;
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   if ((rc = order_after_last(ctx, st))) return rc;
-  rc = enqueue_verify(ctx, n, d_y1, d_y2, d_r1, d_r2, d_s, d_ctx_bytes, d_ctx_off, d_ctx_present,
-                      static_cast<uint8_t*>(d_status_out), st);
+  rc = enqueue_verify(ctx, n, rows, cx, static_cast<uint8_t*>(d_status_out), st);
   if (rc) return rc;
   return record_last(ctx, st);
 }
@@ -2272,8 +2370,8 @@ int cpz_verify_each_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32
                            const void* d_y2, const void* d_r1, const void* d_r2, const void* d_s,
                            const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
                            void* d_status_out, void* stream) {
-  return verify_each_device_flags(ctx, 0, g, h, n, d_y1, d_y2, d_r1, d_r2, d_s, d_ctx_bytes, d_ctx_off, d_ctx_present,
-                                  d_status_out, stream);
+  return verify_each_device_flags(ctx, 0, g, h, n, Rows(d_y1, d_y2, d_r1, d_r2, d_s),
+                                  Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present), d_status_out, stream);
 }
 
 int cpz_verify_each(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const uint8_t* y1,
@@ -2290,7 +2388,7 @@ int cpz_verify_each_ex(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], const 
   if (!ctx || !g || !h) return fail(CPZ_EINVAL, "null context or generators");
   if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
   if (!y1 || !y2 || !r1 || !r2 || !s || !status_out) return fail(CPZ_EINVAL, "null input pointer");
-  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  if (int rc = check_contexts(ctx_bytes, ctx_off, n)) return rc;
   CallLock lock(ctx, flags);
   CPZ_HIP(hipSetDevice(ctx->device));
   int rc = ensure_generators(ctx, g, h, (int64_t)n > var_base_max(ctx));
@@ -2298,32 +2396,22 @@ int cpz_verify_each_ex(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], const 
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
   const uint8_t* host[5] = {y1, y2, r1, r2, s};
   if (n > kPipeChunk) return verify_each_pipelined(ctx, n, host, ctx_bytes, ctx_off, ctx_present, status_out);
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
+  Staged in;
   uint8_t *st_dev = nullptr, *st_host = nullptr;
-  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp,
-                    zero_copy() && (int64_t)n <= kSmallMax, &st_dev, &st_host);
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, in, zero_copy() && (int64_t)n <= kSmallMax,
+                    &st_dev, &st_host);
   if (rc) return rc;
   if (st_dev) {  // zero-copy: inputs read and statuses written through the page-locked block
-    rc = enqueue_verify(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], dcb, dco, dcp, st_dev, ctx->stream);
+    rc = enqueue_verify(ctx, n, in.rows, in.cx, st_dev, ctx->stream);
     if (rc) return rc;
     CPZ_HIP(hipStreamSynchronize(ctx->stream));
     std::memcpy(status_out, st_host, n);
     return CPZ_OK;
   }
   CPZ_HIP(ctx->st.ensure(n));
-  rc = enqueue_verify(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], dcb, dco, dcp,
-                      static_cast<uint8_t*>(ctx->st.p), ctx->stream);
+  rc = enqueue_verify(ctx, n, in.rows, in.cx, static_cast<uint8_t*>(ctx->st.p), ctx->stream);
   if (rc) return rc;
-  // statuses through the page-locked block when stage_inputs used it (its inputs are spent)
-  const bool pinned = ctx->pin.cap >= kPinMail + pad16(n);
-  uint8_t* dst = pinned ? static_cast<uint8_t*>(ctx->pin.p) + kPinMail : status_out;
-  CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  CPZ_HIP(hipStreamSynchronize(ctx->stream));
-  if (pinned) std::memcpy(status_out, dst, n);
-  return CPZ_OK;
+  return read_back_statuses(ctx, n, status_out);
 }
 
 namespace {
@@ -2341,14 +2429,12 @@ void pair_desc(cpz::PairDesc& d, const GenSet& e) {
   std::memcpy(d.c32, e.chal_c32, sizeof(d.c32));
 }
 
-// A mixed-pair range on the device: rows, contexts (absolute offsets into cb), indices and
-// statuses of the whole call, the descriptor table with every pair's tables resident, and the
-// challenge buffer (32 bytes per proof of the call).
+// A mixed-pair range on the device: rows, contexts, indices and statuses of the whole call, the
+// descriptor table with every pair's tables resident, and the challenge buffer (32 bytes per
+// proof of the call).
 struct PairRange {
-  const void* rows[5] = {};  // y1, y2, r1, r2, s
-  const void* cb = nullptr;
-  const uint64_t* co = nullptr;
-  const uint8_t* cp = nullptr;
+  Rows rows;
+  Ctxs cx;
   const uint32_t* idx = nullptr;
   const cpz::PairDesc* desc = nullptr;
   uint32_t* c = nullptr;
@@ -2366,47 +2452,18 @@ int launch_quad_pairs_chunks(cpz_ctx* ctx, const PairRange& r, int64_t lo, int64
   const int64_t chunks = (hi - lo + per - 1) / per;
   const int nst = (int)std::min<int64_t>(CPZ_VERIFY_STREAMS, chunks);
   CPZ_HIP(ctx->scratch.ensure((size_t)CPZ_VERIFY_STREAMS * slab));
-  if (nst > 1) {
-    if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
-    CPZ_HIP(hipEventRecord(ctx->aux_start, st));  // the aux streams start after st's prior work
-    for (int k = 0; k < nst - 1; k++) {
-      if (!ctx->aux_stream[k]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[k], ctx->cus, ctx->device, &ctx->own_queues));
-      if (!ctx->aux_done[k]) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_done[k], hipEventDisableTiming));
-      CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->aux_start, 0));
-    }
-  }
+  if (nst > 1)
+    if (int rc = fork_verify_streams(ctx, st, nst)) return rc;
   for (int64_t c = 0; c < chunks; c++) {
     const int64_t a = lo + c * per;
     const int k = (int)(c % nst);  // stream k owns scratch slab k
     hipStream_t sc = k == 0 ? st : ctx->aux_stream[k - 1];
-    cpz::ChallengeArgs ca{};
-    ca.eq_only = ctx->call_eq ? 1 : 0;
-    ca.n = std::min<int64_t>(hi - a, per);
-    ca.y1 = static_cast<const uint32_t*>(r.rows[0]) + 8 * a;
-    ca.y2 = static_cast<const uint32_t*>(r.rows[1]) + 8 * a;
-    ca.r1 = static_cast<const uint32_t*>(r.rows[2]) + 8 * a;
-    ca.r2 = static_cast<const uint32_t*>(r.rows[3]) + 8 * a;
-    ca.s = static_cast<const uint32_t*>(r.rows[4]) + 8 * a;
-    ca.ctx_bytes = static_cast<const uint8_t*>(r.cb);
-    ca.ctx_off = r.co ? r.co + a : nullptr;  // absolute offsets into ctx_bytes
-    ca.ctx_present = r.cp ? r.cp + a : nullptr;
-    ca.prefix = nullptr;  // per pair: PairDesc
-    ca.c_out = r.c + 8 * a;
-    ca.status_out = r.status + a;
+    const cpz::ChallengeArgs ca =
+        pairs_challenge_args(ctx, std::min<int64_t>(hi - a, per), r.rows.at(a), r.cx.at(a), r.c + 8 * a, r.status + a);
     cpz::PairArgs pa;
     pa.desc = r.desc;
     pa.pair_idx = r.idx + a;
-    cpz::VerifyArgs va{};
-    va.n = ca.n;
-    va.y1 = ca.y1;
-    va.y2 = ca.y2;
-    va.r1 = ca.r1;
-    va.r2 = ca.r2;
-    va.s = ca.s;
-    va.c = ca.c_out;
-    va.status = ca.status_out;
-    va.comb = nullptr;
-    va.eq_only = ca.eq_only;
+    cpz::VerifyArgs va = pairs_verify_args(ca);
     va.quad_max = per;
     va.scratch = static_cast<char*>(ctx->scratch.p) + (size_t)k * slab;
     {
@@ -2416,7 +2473,7 @@ int launch_quad_pairs_chunks(cpz_ctx* ctx, const PairRange& r, int64_t lo, int64
     StageTimer t(ctx, stage, sc);
     CPZ_HIP(cpz::launch_verify_quad_pairs(va, pa, sc));
   }
-  if (nst > 1) return join_verify_streams(ctx, st);
+  if (nst > 1) return join_verify_streams(ctx, st, nst);
   return CPZ_OK;
 }
 
@@ -2429,47 +2486,89 @@ bool pair_resident(const cpz_ctx* ctx, const uint8_t both[64]) {
   return false;
 }
 
-// The argument checks of the bulk mixed-pair calls up to the indices, in cpz_verify_each_pairs_ex's
-// order and wording (the indices follow: on the host, or on the device for the device form).
-int pairs_bulk_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const void* pair_idx,
-                           const void* y1, const void* y2, const void* r1, const void* r2, const void* s,
-                           const void* status_out) {
-  if (!ctx) return fail(CPZ_EINVAL, "null context");
-  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+// ---- argument checks shared by the mixed-pair entry points (each message once) ----------------
+int fail_exceeds(const char* what, size_t v, const char* bound, size_t max) {
+  return fail(CPZ_EINVAL,
+              std::string(what) + " " + std::to_string(v) + " exceeds " + bound + " (" + std::to_string(max) + ")");
+}
+
+// 1 .. max pairs (max: CPZ_PAIRS_MAX, or CPZ_BATCH_PAIRS_MANY_MAX for the many-pair batch check).
+int check_npairs(size_t npairs, size_t max = CPZ_PAIRS_MAX, const char* bound = "CPZ_PAIRS_MAX") {
   if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
-  if (npairs > CPZ_PAIRS_MAX)
-    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
-                                std::to_string(CPZ_PAIRS_MAX) + ")");
-  if (n > CPZ_PAIRS_BULK_MAX_PROOFS)
-    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_PAIRS_BULK_MAX_PROOFS (" +
-                                std::to_string(CPZ_PAIRS_BULK_MAX_PROOFS) + ")");
-  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !status_out)
-    return fail(CPZ_EINVAL, "null input pointer");
+  if (npairs > max) return fail_exceeds("npairs", npairs, bound, max);
   return CPZ_OK;
 }
 
-// Parameters::with_generators (gadgets.rs:77-103) for every pair, on the host, before anything is
-// launched: not the identity, distinct, and -- for a pair without a resident set, whose tables a
-// launch would have to build -- both encodings decode.
-int pairs_bulk_generator_checks(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs) {
-  static const uint8_t zero[32] = {0};
-  for (size_t p = 0; p < npairs; p++) {
-    const uint8_t *g = pairs + 64 * p, *h = g + 32;
-    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
-    if (std::memcmp(g, h, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
-  }
+int fail_pair_idx(size_t i, uint32_t v, size_t npairs) {
+  return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(v) + " is not below npairs (" +
+                              std::to_string(npairs) + ")");
+}
+
+// The kernels trust the indices: every one below npairs, the lowest offending entry named.
+int check_pair_indices(const uint32_t* pair_idx, size_t n, size_t npairs) {
+  for (size_t i = 0; i < n; i++)
+    if (pair_idx[i] >= npairs) return fail_pair_idx(i, pair_idx[i], npairs);
+  return CPZ_OK;
+}
+
+// The same for indices on the device (the context locked, its device current): the lowest
+// offending entry in one word, read back here -- no kernel that follows an index into the
+// descriptor table is enqueued, and no output written, before that.
+int check_pair_indices_device(cpz_ctx* ctx, const uint32_t* d_pair_idx, size_t n, size_t npairs, hipStream_t st) {
+  CPZ_HIP(ctx->bp_word.ensure(2 * sizeof(uint32_t)));
+  uint32_t* word = static_cast<uint32_t*>(ctx->bp_word.p);
+  uint32_t first[2] = {cpz::kPairIdxOk, 0};
+  CPZ_HIP(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
+  CPZ_HIP(cpz::launch_pair_idx_check(d_pair_idx, (int64_t)n, (uint32_t)npairs, word, st));
+  CPZ_HIP(hipMemcpyAsync(&first[0], word, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  if (first[0] == cpz::kPairIdxOk) return CPZ_OK;
+  CPZ_HIP(hipMemcpyAsync(&first[1], d_pair_idx + first[0], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  return fail_pair_idx(first[0], first[1], npairs);
+}
+
+// Parameters::with_generators (gadgets.rs:77-103) for pair p of a list, on the host: not the
+// identity and distinct; then (pair_decodes) both encodings decode.
+int check_pair(size_t p, const uint8_t gh[64]) { return check_generators(gh, gh + 32, pair_tag(p)); }
+
+int fail_pair_decode(size_t p) { return fail(CPZ_EGENERATOR, pair_tag(p) + kGenNoDecode); }
+
+int check_pair_decodes(size_t p, const uint8_t gh[64]) {
+  uint32_t w[16];
+  std::memcpy(w, gh, 64);
+  cpz::ge_p3 pt;
+  if (!cpz::ristretto_decode(pt, w) || !cpz::ristretto_decode(pt, w + 8)) return fail_pair_decode(p);
+  return CPZ_OK;
+}
+
+// check_pair for every pair, before anything is launched or built.
+int check_pairs(size_t npairs, const uint8_t* pairs) {
+  for (size_t p = 0; p < npairs; p++)
+    if (int rc = check_pair(p, pairs + 64 * p)) return rc;
+  return CPZ_OK;
+}
+
+// check_pairs, then -- for a pair without a resident set, whose tables a launch would have to
+// build -- both encodings decode.
+int check_pairs_decode(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs) {
+  if (int rc = check_pairs(npairs, pairs)) return rc;
   CallLock lock(ctx, flags);
-  for (size_t p = 0; p < npairs; p++) {
-    if (pair_resident(ctx, pairs + 64 * p)) continue;
-    uint32_t w[16];
-    std::memcpy(w, pairs + 64 * p, 64);
-    cpz::ge_p3 pt;
-    if (!cpz::ristretto_decode(pt, w) || !cpz::ristretto_decode(pt, w + 8))
-      return fail(CPZ_EGENERATOR,
-                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
-  }
+  for (size_t p = 0; p < npairs; p++)
+    if (!pair_resident(ctx, pairs + 64 * p))
+      if (int rc = check_pair_decodes(p, pairs + 64 * p)) return rc;
+  return CPZ_OK;
+}
+
+// The argument checks of the bulk mixed-pair calls up to the indices, in cpz_verify_each_pairs_ex's
+// order and wording (the indices follow: on the host, or on the device for the device form).
+int pairs_bulk_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const void* pair_idx,
+                           const Rows& rows, const void* status_out, size_t max_n, const char* bound) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+  if (int rc = check_npairs(npairs)) return rc;
+  if (n > max_n) return fail_exceeds("n", n, bound, max_n);
+  if (!pairs || !pair_idx || !rows.complete() || !status_out) return fail(CPZ_EINVAL, "null input pointer");
   return CPZ_OK;
 }
 
@@ -2497,7 +2596,7 @@ bool pairs_build_batch() {
 // Parameters::with_generators (gadgets.rs:77-103) first, per pair without a set, in
 // ensure_generators' order and wording, cpz_last_error naming the lowest offending pair: nothing
 // is launched and no set is invalidated for a list that fails (`decoded`: the caller has
-// decoded the missing pairs' encodings on the host already, pairs_bulk_generator_checks).
+// decoded the missing pairs' encodings on the host already, check_pairs_decode).
 // The call's own resident sets are stamped before any victim is chosen, so none of them is
 // evicted; repeated rows are built once.  ctx->gs ends on the last pair's set.  desc (optional):
 // every pair's descriptor row.  built (optional): the sets built.
@@ -2509,29 +2608,19 @@ int load_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, cpz::PairDesc*
     for (size_t p = 0; p < npairs; p++) {
       const bool had = pair_resident(ctx, pairs + 64 * p);
       int rc = ensure_generators(ctx, pairs + 64 * p, pairs + 64 * p + 32, false, true);
-      if (rc) return fail(rc, "pair " + std::to_string(p) + ": " + g_last_error);
+      if (rc) return fail(rc, pair_tag(p) + g_last_error);
       if (built && !had) *built += 1;
       if (desc) pair_desc(desc[p], *ctx->gs);
     }
     return CPZ_OK;
   }
   // the checks, for every row without a set
-  static const uint8_t zero[32] = {0};
   GenSet* set[CPZ_PAIRS_MAX];
   for (size_t p = 0; p < npairs; p++) {
-    const uint8_t *g = pairs + 64 * p, *h = g + 32;
-    if ((set[p] = find_resident(ctx, g))) continue;
-    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
-    if (std::memcmp(g, h, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
-    if (decoded) continue;
-    uint32_t w[16];
-    std::memcpy(w, g, 64);
-    cpz::ge_p3 pt;
-    if (!cpz::ristretto_decode(pt, w) || !cpz::ristretto_decode(pt, w + 8))
-      return fail(CPZ_EGENERATOR,
-                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
+    if ((set[p] = find_resident(ctx, pairs + 64 * p))) continue;
+    if (int rc = check_pair(p, pairs + 64 * p)) return rc;
+    if (!decoded)
+      if (int rc = check_pair_decodes(p, pairs + 64 * p)) return rc;
   }
   // the call's resident sets stamped, the missing rows deduplicated: row[j] is the first row of
   // the j-th set to build, first[p] the index j of row p's set
@@ -2611,9 +2700,7 @@ int load_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, cpz::PairDesc*
     // (only a pair the caller's own check saw resident and another thread's call evicted since
     // can fail here: every other encoding was decoded on the host above or by the caller)
     for (size_t j = 0; j < nbuild; j++)
-      if (!setup[j].ok[0] || !setup[j].ok[1])
-        return fail(CPZ_EGENERATOR, "pair " + std::to_string(row[j]) +
-                                        ": generator encoding does not decode to a ristretto255 point");
+      if (!setup[j].ok[0] || !setup[j].ok[1]) return fail_pair_decode(row[j]);
     for (size_t j = 0; j < nbuild; j++) {
       GenSet& e = *victim[j];
       const uint8_t* both = pairs + 64 * row[j];
@@ -2636,10 +2723,29 @@ int load_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, cpz::PairDesc*
   return CPZ_OK;
 }
 
-// Every pair of the call resident (light sets at stage 13 unless a full one is cached; no combs)
-// and its descriptor row written to desc[p].
-int pairs_make_resident(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, cpz::PairDesc* desc) {
-  return load_pairs(ctx, npairs, pairs, desc, true, nullptr);
+// Every pair of a host-buffer call resident (light sets at stage 13 unless a full one is cached;
+// no combs), and the block its kernels read: the descriptor table, then the n indices
+// (stage_inputs' extra; staged_pair_args on the device).
+int pairs_resident_block(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, bool decoded, const uint32_t* pair_idx,
+                         size_t n, std::vector<uint8_t>& block) {
+  block.resize(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
+  std::vector<cpz::PairDesc> desc(npairs);
+  if (int rc = load_pairs(ctx, npairs, pairs, desc.data(), decoded, nullptr)) return rc;
+  std::memcpy(block.data(), desc.data(), npairs * sizeof(cpz::PairDesc));
+  std::memcpy(block.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  return CPZ_OK;
+}
+
+// Every pair of a device-buffer call resident (its encodings decoded on the host already), the
+// call ordered on `st` after the last one, and the descriptor table in ctx->bp_desc.
+int pairs_resident_on_device(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, hipStream_t st) {
+  std::vector<cpz::PairDesc> desc(npairs);
+  if (int rc = load_pairs(ctx, npairs, pairs, desc.data(), true, nullptr)) return rc;
+  if (int rc = order_after_last(ctx, st)) return rc;
+  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
+  CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, desc.data(), npairs * sizeof(cpz::PairDesc), hipMemcpyHostToDevice, st));
+  CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `desc` goes
+  return CPZ_OK;
 }
 
 }  // namespace
@@ -2657,31 +2763,13 @@ int cpz_verify_each_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const 
                              const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
                              const uint8_t* ctx_present, uint8_t* status_out) {
   static_assert(CPZ_PAIRS_MAX <= kLightCache, "every pair of a call is resident at once");
-  if (!ctx) return fail(CPZ_EINVAL, "null context");
-  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
-  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
-  if (npairs > CPZ_PAIRS_MAX)
-    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
-                                std::to_string(CPZ_PAIRS_MAX) + ")");
-  if (n > CPZ_PAIRS_MAX_PROOFS || (int64_t)n > kSmallMax)
-    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_PAIRS_MAX_PROOFS (" +
-                                std::to_string(CPZ_PAIRS_MAX_PROOFS) + ")");
-  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !status_out)
-    return fail(CPZ_EINVAL, "null input pointer");
-  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
-  for (size_t i = 0; i < n; i++)
-    if (pair_idx[i] >= npairs)
-      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
-                                  " is not below npairs (" + std::to_string(npairs) + ")");
-  // Parameters::with_generators (gadgets.rs:77-103) for every pair before any table is built
-  static const uint8_t zero[32] = {0};
-  for (size_t p = 0; p < npairs; p++) {
-    const uint8_t *g = pairs + 64 * p, *h = g + 32;
-    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
-    if (std::memcmp(g, h, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
-  }
+  static_assert(kSmallMax >= CPZ_PAIRS_MAX_PROOFS, "the latency kernels take every call of CPZ_PAIRS_MAX_PROOFS proofs");
+  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, pair_idx, Rows(y1, y2, r1, r2, s), status_out,
+                                  CPZ_PAIRS_MAX_PROOFS, "CPZ_PAIRS_MAX_PROOFS");
+  if (rc) return rc;
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  if ((rc = check_pair_indices(pair_idx, n, npairs))) return rc;
+  if ((rc = check_pairs(npairs, pairs))) return rc;  // before any table is built
   if (npairs == 1)
     return cpz_verify_each_ex(ctx, flags, pairs, pairs + 32, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present,
                               status_out);
@@ -2690,54 +2778,23 @@ int cpz_verify_each_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const 
   // Every pair's set, full or light, resident at once (load_pairs: the missing ones built in one
   // pass, the encodings decoded on the host first).  The descriptor table and the indices go to
   // the device in one block (stage_inputs' extra).
-  std::vector<cpz::PairDesc> desc(npairs);
-  int rc = load_pairs(ctx, npairs, pairs, desc.data(), false, nullptr);
-  if (rc) return rc;
-  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
-  std::memcpy(extra.data(), desc.data(), npairs * sizeof(cpz::PairDesc));
-  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  std::vector<uint8_t> extra;
+  if ((rc = pairs_resident_block(ctx, npairs, pairs, false, pair_idx, n, extra))) return rc;
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
   const uint8_t* host[5] = {y1, y2, r1, r2, s};
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
+  Staged in;
   const void* dex = nullptr;
   uint8_t *st_dev = nullptr, *st_host = nullptr;
-  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, zero_copy(), &st_dev,
-                    &st_host, extra.data(), extra.size(), &dex);
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, in, zero_copy(), &st_dev, &st_host, extra.data(),
+                    extra.size(), &dex);
   if (rc) return rc;
   if (!dex) return fail(CPZ_EHIP, "internal: the pair descriptors were not staged");
   if (!st_dev) CPZ_HIP(ctx->st.ensure(n));
   uint8_t* status = st_dev ? st_dev : static_cast<uint8_t*>(ctx->st.p);
-  cpz::ChallengeArgs ca{};
-  ca.eq_only = ctx->call_eq ? 1 : 0;
-  ca.n = (int64_t)n;
-  ca.y1 = static_cast<const uint32_t*>(dev[0]);
-  ca.y2 = static_cast<const uint32_t*>(dev[1]);
-  ca.r1 = static_cast<const uint32_t*>(dev[2]);
-  ca.r2 = static_cast<const uint32_t*>(dev[3]);
-  ca.s = static_cast<const uint32_t*>(dev[4]);
-  ca.ctx_bytes = static_cast<const uint8_t*>(dcb);
-  ca.ctx_off = dco;
-  ca.ctx_present = dcp;
-  ca.prefix = nullptr;  // per pair: PairDesc
-  ca.c_out = nullptr;
-  ca.status_out = status;
-  cpz::VerifyArgs va{};
-  va.n = (int64_t)n;
-  va.y1 = ca.y1;
-  va.y2 = ca.y2;
-  va.r1 = ca.r1;
-  va.r2 = ca.r2;
-  va.s = ca.s;
-  va.c = nullptr;  // computed in the kernel
-  va.status = status;
-  va.comb = nullptr;
-  va.eq_only = ca.eq_only;
-  cpz::PairArgs pa;
-  pa.desc = static_cast<const cpz::PairDesc*>(dex);
-  pa.pair_idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(dex) + npairs * sizeof(cpz::PairDesc));
+  // (no challenge buffer: computed in the kernel)
+  const cpz::ChallengeArgs ca = pairs_challenge_args(ctx, (int64_t)n, in.rows, in.cx, nullptr, status);
+  const cpz::VerifyArgs va = pairs_verify_args(ca);
+  const cpz::PairArgs pa = staged_pair_args(dex, npairs);
   {
     StageTimer span(ctx, 5, ctx->stream);
     if ((rc = launch_verify_chunks(ctx, va, 1, ctx->stream, nullptr, true, &ca, &pa))) return rc;
@@ -2747,12 +2804,7 @@ int cpz_verify_each_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const 
     std::memcpy(status_out, st_host, n);
     return CPZ_OK;
   }
-  const bool pinned = ctx->pin.cap >= kPinMail + pad16(n);
-  uint8_t* dst = pinned ? static_cast<uint8_t*>(ctx->pin.p) + kPinMail : status_out;
-  CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  CPZ_HIP(hipStreamSynchronize(ctx->stream));
-  if (pinned) std::memcpy(status_out, dst, n);
-  return CPZ_OK;
+  return read_back_statuses(ctx, n, status_out);
 }
 
 int cpz_verify_each_pairs_bulk(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const uint32_t* pair_idx,
@@ -2768,14 +2820,12 @@ int cpz_verify_each_pairs_bulk_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, c
                                   const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes,
                                   const uint64_t* ctx_off, const uint8_t* ctx_present, uint8_t* status_out) {
   static_assert(CPZ_PAIRS_MAX <= kLightCache, "every pair of a call is resident at once");
-  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, status_out);
+  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, pair_idx, Rows(y1, y2, r1, r2, s), status_out,
+                                  CPZ_PAIRS_BULK_MAX_PROOFS, "CPZ_PAIRS_BULK_MAX_PROOFS");
   if (rc) return rc;
-  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
-  for (size_t i = 0; i < n; i++)
-    if (pair_idx[i] >= npairs)
-      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
-                                  " is not below npairs (" + std::to_string(npairs) + ")");
-  if ((rc = pairs_bulk_generator_checks(ctx, flags, npairs, pairs))) return rc;
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  if ((rc = check_pair_indices(pair_idx, n, npairs))) return rc;
+  if ((rc = check_pairs_decode(ctx, flags, npairs, pairs))) return rc;
   if (npairs == 1)
     return cpz_verify_each_ex(ctx, flags, pairs, pairs + 32, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present,
                               status_out);
@@ -2785,32 +2835,25 @@ int cpz_verify_each_pairs_bulk_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, c
   CallLock lock(ctx, flags);
   CPZ_HIP(hipSetDevice(ctx->device));
   // every pair resident at once, then the descriptor table and the indices to the device in one
-  // block with the rows (stage_inputs' extra), as cpz_verify_batch_pairs_ex stages them
-  std::vector<cpz::PairDesc> desc(npairs);
-  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
-  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
-  std::memcpy(extra.data(), desc.data(), npairs * sizeof(cpz::PairDesc));
-  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  // block with the rows (stage_inputs' extra), as the mixed-pair batch check stages them
+  std::vector<uint8_t> extra;
+  if ((rc = pairs_resident_block(ctx, npairs, pairs, true, pair_idx, n, extra))) return rc;
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
   const uint8_t* host[5] = {y1, y2, r1, r2, s};
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
+  Staged in;
   const void* dex = nullptr;
-  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, false, nullptr, nullptr,
-                    extra.data(), extra.size(), &dex);
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, in, false, nullptr, nullptr, extra.data(),
+                    extra.size(), &dex);
   if (rc) return rc;
   if (!dex) return fail(CPZ_EHIP, "internal: the pair descriptors were not staged");
   CPZ_HIP(ctx->st.ensure(n));
   CPZ_HIP(ctx->c.ensure(n * 32));
+  const cpz::PairArgs pa = staged_pair_args(dex, npairs);
   PairRange r;
-  for (int k = 0; k < 5; k++) r.rows[k] = dev[k];
-  r.cb = dcb;
-  r.co = dco;
-  r.cp = dcp;
-  r.desc = static_cast<const cpz::PairDesc*>(dex);
-  r.idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(dex) + npairs * sizeof(cpz::PairDesc));
+  r.rows = in.rows;
+  r.cx = in.cx;
+  r.desc = pa.desc;
+  r.idx = pa.pair_idx;
   r.c = static_cast<uint32_t*>(ctx->c.p);
   r.status = static_cast<uint8_t*>(ctx->st.p);
   {
@@ -2820,12 +2863,7 @@ int cpz_verify_each_pairs_bulk_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, c
       return rc;
     }
   }
-  const bool pinned = ctx->pin.cap >= kPinMail + pad16(n);
-  uint8_t* dst = pinned ? static_cast<uint8_t*>(ctx->pin.p) + kPinMail : status_out;
-  CPZ_HIP(hipMemcpyAsync(dst, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
-  CPZ_HIP(hipStreamSynchronize(ctx->stream));
-  if (pinned) std::memcpy(status_out, dst, n);
-  return CPZ_OK;
+  return read_back_statuses(ctx, n, status_out);
 }
 
 int cpz_verify_each_pairs_device(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
@@ -2833,59 +2871,35 @@ int cpz_verify_each_pairs_device(cpz_ctx* ctx, uint32_t flags, size_t npairs, co
                                  const void* d_r2, const void* d_s, const void* d_ctx_bytes,
                                  const uint64_t* d_ctx_off, const uint8_t* d_ctx_present, void* d_status_out,
                                  void* stream) {
-  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, d_pair_idx, d_y1, d_y2, d_r1, d_r2, d_s, d_status_out);
+  const Rows rows(d_y1, d_y2, d_r1, d_r2, d_s);
+  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, d_pair_idx, rows, d_status_out, CPZ_PAIRS_BULK_MAX_PROOFS,
+                                  "CPZ_PAIRS_BULK_MAX_PROOFS");
   if (rc) return rc;
-  if (!aligned16(d_y1) || !aligned16(d_y2) || !aligned16(d_r1) || !aligned16(d_r2) || !aligned16(d_s))
-    return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
+  if (!rows.aligned()) return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
   if ((reinterpret_cast<uintptr_t>(d_pair_idx) & 3) != 0) return fail(CPZ_EINVAL, "d_pair_idx must be 4-byte aligned");
-  if (d_ctx_off && !d_ctx_bytes) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  if ((rc = check_contexts(d_ctx_bytes, d_ctx_off, n, true))) return rc;
   hipStream_t st = nullptr;
   {
-    // The indices, on the device: the lowest offending entry in one word, read back here -- no
-    // kernel that follows an index into the descriptor table is enqueued before that.
     CallLock lock(ctx, flags);
     CPZ_HIP(hipSetDevice(ctx->device));
     st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     if ((rc = order_after_last(ctx, st))) return rc;
-    CPZ_HIP(ctx->bp_word.ensure(2 * sizeof(uint32_t)));
-    uint32_t* word = static_cast<uint32_t*>(ctx->bp_word.p);
-    uint32_t first[2] = {cpz::kPairIdxOk, 0};
-    CPZ_HIP(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
-    CPZ_HIP(cpz::launch_pair_idx_check(d_pair_idx, (int64_t)n, (uint32_t)npairs, word, st));
-    CPZ_HIP(hipMemcpyAsync(&first[0], word, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CPZ_HIP(hipStreamSynchronize(st));
-    if (first[0] != cpz::kPairIdxOk) {
-      CPZ_HIP(hipMemcpyAsync(&first[1], d_pair_idx + first[0], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      CPZ_HIP(hipStreamSynchronize(st));
-      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(first[0]) + "] = " + std::to_string(first[1]) +
-                                  " is not below npairs (" + std::to_string(npairs) + ")");
-    }
+    if ((rc = check_pair_indices_device(ctx, d_pair_idx, n, npairs, st))) return rc;
   }
-  if ((rc = pairs_bulk_generator_checks(ctx, flags, npairs, pairs))) return rc;
+  if ((rc = check_pairs_decode(ctx, flags, npairs, pairs))) return rc;
   if (npairs == 1) {
-    rc = verify_each_device_flags(ctx, flags, pairs, pairs + 32, n, d_y1, d_y2, d_r1, d_r2, d_s, d_ctx_bytes, d_ctx_off,
-                                  d_ctx_present, d_status_out, stream);
+    rc = verify_each_device_flags(ctx, flags, pairs, pairs + 32, n, rows, Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present),
+                                  d_status_out, stream);
     if (rc) return rc;
     CPZ_HIP(hipStreamSynchronize(st));
     return CPZ_OK;
   }
   CallLock lock(ctx, flags);
-  std::vector<cpz::PairDesc> desc(npairs);
-  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
-  if ((rc = order_after_last(ctx, st))) return rc;
-  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
-  CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, desc.data(), npairs * sizeof(cpz::PairDesc), hipMemcpyHostToDevice, st));
-  CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `desc` goes
+  if ((rc = pairs_resident_on_device(ctx, npairs, pairs, st))) return rc;
   CPZ_HIP(ctx->c.ensure(n * 32));
   PairRange r;
-  r.rows[0] = d_y1;
-  r.rows[1] = d_y2;
-  r.rows[2] = d_r1;
-  r.rows[3] = d_r2;
-  r.rows[4] = d_s;
-  r.cb = d_ctx_bytes;
-  r.co = d_ctx_off;
-  r.cp = d_ctx_off ? d_ctx_present : nullptr;
+  r.rows = rows;
+  r.cx = Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_off ? d_ctx_present : nullptr);
   r.desc = static_cast<const cpz::PairDesc*>(ctx->bp_desc.p);
   r.idx = d_pair_idx;
   r.c = static_cast<uint32_t*>(ctx->c.p);
@@ -2906,10 +2920,7 @@ int cpz_verify_each_pairs_device(cpz_ctx* ctx, uint32_t flags, size_t npairs, co
 int cpz_ctx_load_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t* built_out) {
   if (built_out) *built_out = 0;
   if (!ctx) return fail(CPZ_EINVAL, "null context");
-  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
-  if (npairs > CPZ_PAIRS_MAX)
-    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
-                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (int rc = check_npairs(npairs)) return rc;
   if (!pairs) return fail(CPZ_EINVAL, "null input pointer");
   CallLock lock(ctx);
   CPZ_HIP(hipSetDevice(ctx->device));
@@ -2918,10 +2929,7 @@ int cpz_ctx_load_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t
 
 int cpz_ctx_pairs_resident(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, uint8_t* resident_out) {
   if (!ctx) return fail(CPZ_EINVAL, "null context");
-  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
-  if (npairs > CPZ_PAIRS_MAX)
-    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
-                                std::to_string(CPZ_PAIRS_MAX) + ")");
+  if (int rc = check_npairs(npairs)) return rc;
   if (!pairs || !resident_out) return fail(CPZ_EINVAL, "null input pointer");
   CallLock lock(ctx);
   for (size_t p = 0; p < npairs; p++) resident_out[p] = pair_resident(ctx, pairs + 64 * p) ? 1 : 0;
@@ -2955,10 +2963,8 @@ struct PairBatch {
   int64_t n = 0;
   const uint8_t* pairs = nullptr;         // host: npairs x (g, h)
   const uint32_t* pair_idx = nullptr;     // host
-  const void* rows[5] = {};               // device: y1, y2, r1, r2, s
-  const void* cb = nullptr;               // device contexts (stage_inputs)
-  const uint64_t* co = nullptr;
-  const uint8_t* cp = nullptr;
+  Rows rows;                              // device
+  Ctxs cx;                                // device contexts (stage_inputs)
   const uint32_t* d_idx = nullptr;        // device: n indices
   uint8_t* d_status = nullptr;
   const cpz::PairDesc* d_full = nullptr;  // device descriptors with tables, set at the first leaf
@@ -3002,6 +3008,15 @@ int pairs_range_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi,
   return CPZ_OK;
 }
 
+// pairs_range_launch over [lo, hi), then its identity flag read back (synchronises): a part of
+// the bisection.
+int pairs_part_identity(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi, hipStream_t st, int* ident) {
+  if (int rc = pairs_range_launch(ctx, b, lo, hi, st)) return rc;
+  CPZ_HIP(hipMemcpyAsync(ident, ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  return CPZ_OK;
+}
+
 // Per-proof verification of [lo, hi) under every entry's own pair, on the rows already on the
 // device: up to CPZ_PAIRS_MAX_PROOFS the mixed-pair latency kernels, above (a range most of whose
 // parts failed) the chunked eight-lane path of cpz_verify_each_pairs_bulk.  The first leaf makes
@@ -3034,10 +3049,8 @@ int pairs_verify_range(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipSt
   const char* leaf_quad = std::getenv("CPZ_PAIRS_LEAF_QUAD");
   if (hi - lo > (int64_t)CPZ_PAIRS_MAX_PROOFS && !(leaf_quad && leaf_quad[0] == '0')) {
     PairRange r;
-    for (int k = 0; k < 5; k++) r.rows[k] = b.rows[k];
-    r.cb = b.cb;
-    r.co = b.co;
-    r.cp = b.cp;
+    r.rows = b.rows;
+    r.cx = b.cx;
     r.idx = b.d_idx;
     r.desc = b.d_full;
     r.c = static_cast<uint32_t*>(ctx->c.p);  // n x 32, the batch's challenges: rewritten with the same values
@@ -3046,31 +3059,9 @@ int pairs_verify_range(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipSt
   }
   for (int64_t a = lo; a < hi; a += CPZ_PAIRS_MAX_PROOFS) {
     const int64_t m = std::min<int64_t>(hi - a, CPZ_PAIRS_MAX_PROOFS);
-    cpz::ChallengeArgs ca{};
-    ca.eq_only = ctx->call_eq ? 1 : 0;
-    ca.n = m;
-    ca.y1 = static_cast<const uint32_t*>(b.rows[0]) + 8 * a;
-    ca.y2 = static_cast<const uint32_t*>(b.rows[1]) + 8 * a;
-    ca.r1 = static_cast<const uint32_t*>(b.rows[2]) + 8 * a;
-    ca.r2 = static_cast<const uint32_t*>(b.rows[3]) + 8 * a;
-    ca.s = static_cast<const uint32_t*>(b.rows[4]) + 8 * a;
-    ca.ctx_bytes = static_cast<const uint8_t*>(b.cb);
-    ca.ctx_off = b.co ? b.co + a : nullptr;  // absolute offsets into ctx_bytes
-    ca.ctx_present = b.cp ? b.cp + a : nullptr;
-    ca.prefix = nullptr;  // per pair: PairDesc
-    ca.c_out = nullptr;
-    ca.status_out = b.d_status + a;
-    cpz::VerifyArgs va{};
-    va.n = m;
-    va.y1 = ca.y1;
-    va.y2 = ca.y2;
-    va.r1 = ca.r1;
-    va.r2 = ca.r2;
-    va.s = ca.s;
-    va.c = nullptr;  // computed in the kernel
-    va.status = b.d_status + a;
-    va.comb = nullptr;
-    va.eq_only = ca.eq_only;
+    // (no challenge buffer: computed in the kernel)
+    const cpz::ChallengeArgs ca = pairs_challenge_args(ctx, m, b.rows.at(a), b.cx.at(a), nullptr, b.d_status + a);
+    const cpz::VerifyArgs va = pairs_verify_args(ca);
     cpz::PairArgs pa;
     pa.desc = b.d_full;
     pa.pair_idx = b.d_idx + a;
@@ -3092,22 +3083,11 @@ int pairs_verify_listed(cpz_ctx* ctx, const PairBatch& b, const uint32_t* d_list
   const int64_t chunks = (nb + per - 1) / per;
   const int nst = (int)std::min<int64_t>(CPZ_VERIFY_STREAMS, chunks);
   CPZ_HIP(ctx->scratch.ensure((size_t)CPZ_VERIFY_STREAMS * slab));
-  if (nst > 1) {
-    if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
-    CPZ_HIP(hipEventRecord(ctx->aux_start, st));
-    for (int k = 0; k < nst - 1; k++) {
-      if (!ctx->aux_stream[k]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[k], ctx->cus, ctx->device, &ctx->own_queues));
-      if (!ctx->aux_done[k]) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_done[k], hipEventDisableTiming));
-      CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[k], ctx->aux_start, 0));
-    }
-  }
+  if (nst > 1)
+    if (int rc = fork_verify_streams(ctx, st, nst)) return rc;
   cpz::VerifyArgs va{};
   va.n = b.n;
-  va.y1 = static_cast<const uint32_t*>(b.rows[0]);
-  va.y2 = static_cast<const uint32_t*>(b.rows[1]);
-  va.r1 = static_cast<const uint32_t*>(b.rows[2]);
-  va.r2 = static_cast<const uint32_t*>(b.rows[3]);
-  va.s = static_cast<const uint32_t*>(b.rows[4]);
+  set_rows(va, b.rows);
   va.c = static_cast<const uint32_t*>(ctx->c.p);
   va.status = b.d_status;
   va.eq_only = ctx->call_eq ? 1 : 0;
@@ -3126,7 +3106,7 @@ int pairs_verify_listed(cpz_ctx* ctx, const PairBatch& b, const uint32_t* d_list
     StageTimer t(ctx, 1, sc);
     CPZ_HIP(cpz::launch_verify_quad_pairs(v, pa, sc));
   }
-  if (nst > 1) return join_verify_streams(ctx, st);
+  if (nst > 1) return join_verify_streams(ctx, st, nst);
   return CPZ_OK;
 }
 
@@ -3207,10 +3187,7 @@ constexpr int kPairGuardAfter = 3;  // failing parts before the sample is launch
 int pairs_guard_launch(cpz_ctx* ctx, const PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
   const int64_t nblk = (hi - lo + cpz::kPartProofs - 1) / cpz::kPartProofs;
   const int64_t s0 = lo + (nblk - kPairGuardBlocks) / 2 * cpz::kPartProofs;  // whole blocks, inside [lo, hi)
-  if (!ctx->aux_start) CPZ_HIP(hipEventCreateWithFlags(&ctx->aux_start, hipEventDisableTiming));
-  if (!ctx->aux_stream[0]) CPZ_HIP(stream_own_queue(&ctx->aux_stream[0], ctx->cus, ctx->device, &ctx->own_queues));
-  CPZ_HIP(hipEventRecord(ctx->aux_start, st));  // after the prepare
-  CPZ_HIP(hipStreamWaitEvent(ctx->aux_stream[0], ctx->aux_start, 0));
+  if (int rc = fork_verify_streams(ctx, st, 2)) return rc;  // the first aux stream, after the prepare
   PartPairs px;
   return pairs_part_pass(ctx, b, s0, s0 + kPairGuardBlocks * cpz::kPartProofs, ctx->aux_stream[0], px, false);
 }
@@ -3228,105 +3205,68 @@ int pairs_guard_read(cpz_ctx* ctx, int* failing) {
 int pairs_part(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st) {
   const int64_t n = hi - lo;
   const int64_t nblk = (n + cpz::kPartProofs - 1) / cpz::kPartProofs;
-  const int64_t blo = lo / cpz::kPartProofs;
   PartPairs px;
   if (int rc = pairs_part_pass(ctx, b, lo, hi, st, px, true)) return rc;
-  std::vector<uint8_t> dirty((size_t)nblk);
-  CPZ_HIP(hipMemcpyAsync(dirty.data(), ctx->pt_fail.p, (size_t)nblk, hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipStreamSynchronize(st));
   std::vector<uint32_t> blocks;
-  for (int64_t k = 0; k < nblk; k++)
-    if (dirty[(size_t)k]) blocks.push_back((uint32_t)k);
-  ctx->fb_stats[2] += (uint64_t)nblk;
-  ctx->fb_stats[3] += blocks.size();
+  if (int rc = part_failing_blocks(ctx, nblk, blocks, st)) return rc;
   if (blocks.empty()) return CPZ_OK;
   if (2 * (int64_t)blocks.size() > nblk) return pairs_leaf(ctx, b, lo, hi, st);  // dense: today's path
   if (int rc = pairs_resident(ctx, b, st)) return rc;
   CPZ_HIP(hipMemcpyAsync(ctx->pt_blocks.p, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   std::vector<uint32_t> whole = blocks, cand;
   if (CPZ_PART_LOCATE) {
-    int rc = part_locate(ctx, n, static_cast<const uint32_t*>(b.rows[4]) + 8 * lo, b.d_status + lo, b.seed,
-                         b.first_index + (uint64_t)lo, blocks, whole, cand, st, &px);
+    int rc = part_locate(ctx, n, b.rows.s + 8 * lo, b.d_status + lo, b.seed, b.first_index + (uint64_t)lo, blocks, whole,
+                         cand, st, &px);
     if (rc) return rc;
   }
   // the per-proof passes take entries and blocks of the whole batch
-  uint32_t* d_list = static_cast<uint32_t*>(ctx->pt_blocks.p) + blocks.size();
-  StageTimer span(ctx, 4, st);
-  if (!cand.empty()) {
-    ctx->fb_stats[4] += (uint64_t)cand.size();
-    std::vector<uint32_t> ge(cand.size());
-    for (size_t k = 0; k < cand.size(); k++) ge[k] = cand[k] + (uint32_t)lo;
-    CPZ_HIP(hipMemcpyAsync(d_list, ge.data(), ge.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (int rc = pairs_verify_listed(ctx, b, d_list, (int64_t)ge.size(), 1, st)) return rc;
-    std::vector<uint8_t> cst(ge.size());
-    uint8_t* d_cst = static_cast<uint8_t*>(ctx->pt_lfail.p);  // |cand| <= failing blocks bytes, spent
-    CPZ_HIP(cpz::launch_gather_status(b.d_status, d_list, (int64_t)ge.size(), d_cst, st));
-    CPZ_HIP(hipMemcpyAsync(cst.data(), d_cst, ge.size(), hipMemcpyDeviceToHost, st));
-    CPZ_HIP(hipStreamSynchronize(st));
-    for (size_t k = 0; k < cand.size(); k++)
-      if (cst[k] == cpz::kStatusOk) whole.push_back(cand[k] / (uint32_t)cpz::kPartProofs);
-  }
-  if (whole.empty()) return CPZ_OK;
-  std::vector<uint32_t> gw(whole.size());
-  for (size_t k = 0; k < whole.size(); k++) {
-    gw[k] = whole[k] + (uint32_t)blo;
-    ctx->fb_stats[4] += (uint64_t)std::min<int64_t>(cpz::kPartProofs, n - (int64_t)whole[k] * cpz::kPartProofs);
-  }
-  CPZ_HIP(hipMemcpyAsync(d_list, gw.data(), gw.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (int rc = pairs_verify_listed(ctx, b, d_list, (int64_t)gw.size(), cpz::kPartProofs, st)) return rc;
-  CPZ_HIP(hipStreamSynchronize(st));  // the host lists are pageable memory read by the copies above
-  return CPZ_OK;
+  return part_verify_lists(ctx, n, lo, b.d_status, blocks.size(), whole, cand, st,
+                           [&](const uint32_t* d_list, int64_t nb, int block_proofs) {
+                             return pairs_verify_listed(ctx, b, d_list, nb, block_proofs, st);
+                           });
 }
 
-// rlc_fallback for a mixed-pair batch: the same fan-out-8 bisection aligned to kRlcPrepBlock, each
-// part's partial one more MSM over the prepared points with that part's per-pair extras.
-int pairs_fallback(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipStream_t st, int depth) {
-  if (hi - lo <= (int64_t)CPZ_PAIRS_MAX_PROOFS || depth > 12) return pairs_leaf(ctx, b, lo, hi, st);
-  int64_t cuts[kFanout + 1];
-  for (int k = 0; k <= kFanout; k++) {
-    int64_t c = lo + ((hi - lo) * k) / kFanout;
-    c = (c / cpz::kRlcPrepBlock) * cpz::kRlcPrepBlock;
-    cuts[k] = k == 0 ? lo : (k == kFanout ? hi : (c < lo ? lo : c));
+// The bisection (bisect) over a mixed-pair batch of at most CPZ_PAIRS_MAX pairs: each part's
+// partial one more MSM over the prepared points with that part's per-pair extras, leaves of
+// CPZ_PAIRS_MAX_PROOFS entries, and the guard above -- its sample launched at the
+// kPairGuardAfter-th failing part of a range that may end in pairs_part, read once every part's
+// MSM is done, and at the dense decision sending the range there if the sample is clean.
+struct PairsRoute : BisectRoute {
+  cpz_ctx* ctx;
+  PairBatch* b;
+  hipStream_t st;
+  bool sampled = false;  // (of the range whose parts are running: no recursion before parts_done)
+  bool leaf(int64_t lo, int64_t hi) const { return hi - lo <= (int64_t)CPZ_PAIRS_MAX_PROOFS; }
+  int part_identity(int64_t lo, int64_t hi, int* ident) { return pairs_part_identity(ctx, *b, lo, hi, st, ident); }
+  int per_proof(int64_t lo, int64_t hi) { return pairs_leaf(ctx, *b, lo, hi, st); }
+  int part_failed(int64_t lo, int64_t hi, int nfail) {
+    static_assert(CPZ_BATCH_PAIRS_PART_MIN >= 2 * kPairGuardBlocks * cpz::kPartProofs,
+                  "the guard's sample lies inside the range");
+    static_assert(2 * kPairGuardAfter <= kFanout + 1, "the dense branch is reached only with the sample launched");
+    if (hi - lo < (int64_t)CPZ_BATCH_PAIRS_PART_MIN || sampled || nfail != kPairGuardAfter) return CPZ_OK;
+    sampled = true;
+    return pairs_guard_launch(ctx, *b, lo, hi, st);
   }
-  static_assert(CPZ_BATCH_PAIRS_PART_MIN >= 2 * kPairGuardBlocks * cpz::kPartProofs, "the guard's sample lies inside the range");
-  const bool guard = hi - lo >= (int64_t)CPZ_BATCH_PAIRS_PART_MIN;  // may end in pairs_part
-  bool sampled = false;
-  bool failing[kFanout];
-  int nfail = 0;
-  for (int k = 0; k < kFanout; k++) {
-    failing[k] = false;
-    if (cuts[k + 1] <= cuts[k]) continue;
-    if (int rc = pairs_range_launch(ctx, b, cuts[k], cuts[k + 1], st)) return rc;
-    int ident = 0;
-    CPZ_HIP(hipMemcpyAsync(&ident, ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    CPZ_HIP(hipStreamSynchronize(st));
-    ctx->fb_stats[5] += 1;
-    failing[k] = !ident;
-    nfail += failing[k] ? 1 : 0;
-    if (guard && !sampled && nfail == kPairGuardAfter) {
-      if (int rc = pairs_guard_launch(ctx, b, lo, hi, st)) return rc;
-      sampled = true;
-    }
-  }
-  static_assert(2 * kPairGuardAfter <= kFanout + 1, "the dense branch is reached only with the sample launched");
-  int sample_bad = 0;
-  if (sampled)  // also: the sample's buffers are free again before anything below reuses them
+  int parts_done(int64_t lo, int64_t hi, bool dense, bool* taken) {
+    if (!sampled) return CPZ_OK;
+    sampled = false;
+    int sample_bad = 0;  // also: the sample's buffers are free again before anything below reuses them
     if (int rc = pairs_guard_read(ctx, &sample_bad)) return rc;
-  if (2 * nfail > kFanout) {  // dense failures: no pruning left
-    if (sampled) {
-      ctx->fb_stats[1] += (uint64_t)sample_bad;
-      if (2 * sample_bad <= kPairGuardBlocks) {
-        ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
-        return pairs_part(ctx, b, lo, hi, st);
-      }
-    }
-    return pairs_leaf(ctx, b, lo, hi, st);
+    if (!dense) return CPZ_OK;
+    ctx->fb_stats[1] += (uint64_t)sample_bad;
+    if (2 * sample_bad > kPairGuardBlocks) return CPZ_OK;  // per proof, as without the guard
+    ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
+    *taken = true;
+    return pairs_part(ctx, *b, lo, hi, st);
   }
-  for (int k = 0; k < kFanout; k++) {
-    if (!failing[k]) continue;
-    if (int rc = pairs_fallback(ctx, b, cuts[k], cuts[k + 1], st, depth + 1)) return rc;
-  }
-  return CPZ_OK;
+};
+
+int pairs_fallback(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
+  PairsRoute r;
+  r.ctx = ctx;
+  r.b = &b;
+  r.st = st;
+  return bisect(ctx, r, 0, b.n, 0);
 }
 
 // ---- more than CPZ_PAIRS_MAX pairs (cpz_verify_batch_pairs_many) ----------------------------
@@ -3375,45 +3315,227 @@ bool pairs_many_distinct_over(const PairBatch& b, ManyRuns& ms, int64_t lo, int6
   return cpz::pair_run_end(b.pair_idx, lo, hi, ms.stamp.data(), ++ms.tag, CPZ_PAIRS_MAX, run, &k) < hi;
 }
 
-// pairs_fallback without the partitioned branch (part.hip's lists hold CPZ_PAIRS_MAX pairs).
+// PairsRoute without the guard and the partitioned branch (part.hip's lists hold CPZ_PAIRS_MAX pairs).
 // ms.deep (the default): a range of at most CPZ_PAIRS_MAX_PROOFS entries that still holds more than
 // CPZ_PAIRS_MAX distinct pairs is bisected further, down to single weight blocks, instead of being
 // verified in runs -- a sub-range MSM costs less than the table sets of the pairs it clears.
 // CPZ_PAIRS_MANY_DEEP=0 in the environment, read at every call, stops at CPZ_PAIRS_MAX_PROOFS as
-// pairs_fallback does: for measurement (tools/batch_pairs_many_ab.py).
-int pairs_many_fallback(cpz_ctx* ctx, PairBatch& b, ManyRuns& ms, int64_t lo, int64_t hi, hipStream_t st, int depth) {
-  bool leaf = hi - lo <= (int64_t)CPZ_PAIRS_MAX_PROOFS || depth > 12;
-  if (leaf && ms.deep && depth <= 12 && hi - lo > (int64_t)cpz::kRlcPrepBlock && pairs_many_distinct_over(b, ms, lo, hi))
-    leaf = false;
-  if (leaf) return pairs_many_leaf(ctx, b, ms, lo, hi, st);
-  int64_t cuts[kFanout + 1];
-  for (int k = 0; k <= kFanout; k++) {
-    int64_t c = lo + ((hi - lo) * k) / kFanout;
-    c = (c / cpz::kRlcPrepBlock) * cpz::kRlcPrepBlock;
-    cuts[k] = k == 0 ? lo : (k == kFanout ? hi : (c < lo ? lo : c));
+// PairsRoute does: for measurement (tools/batch_pairs_many_ab.py).
+struct ManyRoute : BisectRoute {
+  static constexpr bool kBlockParts = true;  // (the deep policy alone cuts a range that small)
+  cpz_ctx* ctx;
+  PairBatch* b;
+  ManyRuns* ms;
+  hipStream_t st;
+  bool leaf(int64_t lo, int64_t hi) {
+    if (hi - lo > (int64_t)CPZ_PAIRS_MAX_PROOFS) return false;
+    return !(ms->deep && hi - lo > (int64_t)cpz::kRlcPrepBlock && pairs_many_distinct_over(*b, *ms, lo, hi));
   }
-  // at most kFanout weight blocks (the deep policy alone gets here): a part per block, so that a
-  // range just above one block is still cut (lo is a multiple of the block)
-  if (hi - lo <= (int64_t)kFanout * cpz::kRlcPrepBlock)
-    for (int k = 1; k <= kFanout; k++) cuts[k] = std::min<int64_t>(lo + (int64_t)k * cpz::kRlcPrepBlock, hi);
-  bool failing[kFanout];
-  int nfail = 0;
-  for (int k = 0; k < kFanout; k++) {
-    failing[k] = false;
-    if (cuts[k + 1] <= cuts[k]) continue;
-    if (int rc = pairs_range_launch(ctx, b, cuts[k], cuts[k + 1], st)) return rc;
-    int ident = 0;
-    CPZ_HIP(hipMemcpyAsync(&ident, ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  int part_identity(int64_t lo, int64_t hi, int* ident) { return pairs_part_identity(ctx, *b, lo, hi, st, ident); }
+  int per_proof(int64_t lo, int64_t hi) { return pairs_many_leaf(ctx, *b, *ms, lo, hi, st); }
+};
+
+int pairs_many_fallback(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
+  ManyRuns ms;
+  ms.stamp.assign(b.npairs, 0);
+  ms.rows.resize(64 * CPZ_PAIRS_MAX);
+  ms.full.resize(CPZ_PAIRS_MAX);
+  const char* deep = std::getenv("CPZ_PAIRS_MANY_DEEP");
+  ms.deep = !(deep && deep[0] == '0');
+  ManyRoute r;
+  r.ctx = ctx;
+  r.b = &b;
+  r.ms = &ms;
+  r.st = st;
+  return bisect(ctx, r, 0, b.n, 0);
+}
+
+// Per-pair set-up of a batch over at most CPZ_PAIRS_MAX pairs, no table: one launch for the
+// snapshots and the pairs' Niels points, one copy back for the snapshots and decode flags (timed
+// inside stage 2).  `extra` receives what goes to the device in one block with the rows
+// (stage_inputs' extra; staged_pair_args): the descriptors (null tables) with the host-derived
+// fixed-schedule masks, then the indices.
+int pairs_setup_host(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, const uint32_t* pair_idx, size_t n,
+                     hipStream_t st, std::vector<uint8_t>& extra) {
+  CPZ_HIP(ctx->bp_gh.ensure(npairs * 64));
+  CPZ_HIP(ctx->bp_setup.ensure(npairs * sizeof(cpz::PairSetup)));
+  CPZ_HIP(ctx->bp_pts.ensure(2 * npairs * sizeof(cpz::ge_niels)));
+  std::vector<cpz::PairSetup> setup(npairs);
+  {
+    StageTimer t(ctx, 2, st);
+    CPZ_HIP(hipMemcpyAsync(ctx->bp_gh.p, pairs, npairs * 64, hipMemcpyHostToDevice, st));
+    CPZ_HIP(cpz::launch_pair_setup(static_cast<const uint32_t*>(ctx->bp_gh.p), (int)npairs,
+                                   static_cast<cpz::PairSetup*>(ctx->bp_setup.p),
+                                   static_cast<cpz::ge_niels*>(ctx->bp_pts.p), st));
+    CPZ_HIP(hipMemcpyAsync(setup.data(), ctx->bp_setup.p, npairs * sizeof(cpz::PairSetup), hipMemcpyDeviceToHost, st));
+  }
+  CPZ_HIP(hipStreamSynchronize(st));
+  for (size_t p = 0; p < npairs; p++)
+    if (!setup[p].ok[0] || !setup[p].ok[1]) return fail_pair_decode(p);
+  extra.resize(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
+  uint32_t k1[50], k2[50];
+  const bool masks = cpz::challenge_masks(k1, k2);
+  for (size_t p = 0; p < npairs; p++) {
+    cpz::PairDesc d{};
+    std::memcpy(d.prefix, setup[p].prefix, sizeof(d.prefix));
+    words_from_bytes(d.gh_words, pairs + 64 * p, pairs + 64 * p + 32);
+    d.fast_noctx = masks && cpz::challenge_prefix_is_fixed(d.prefix[1]) ? 1 : 0;
+    std::memcpy(d.k1, k1, sizeof(d.k1));
+    std::memcpy(d.k2, k2, sizeof(d.k2));
+    d.fast_ctx32 = cpz::challenge_prefix_is_ctx32(d.prefix[0]) &&
+                           cpz::challenge_masks_ctx32(d.c32, d.gh_words, d.gh_words + 8)
+                       ? 1
+                       : 0;
+    std::memcpy(extra.data() + p * sizeof(cpz::PairDesc), &d, sizeof(d));
+  }
+  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
+  return CPZ_OK;
+}
+
+// The same for more pairs, on the device: the table-less descriptor rows (ctx->bp_desc), the
+// pairs' Niels points and the decode flags, which alone come back (timed inside stage 2, as
+// k_pair_setup is).
+int pairs_setup_device(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, hipStream_t st) {
+  CPZ_HIP(ctx->bp_gh.ensure(npairs * 64));
+  CPZ_HIP(ctx->bp_ok.ensure(npairs * 2 * sizeof(int32_t)));
+  CPZ_HIP(ctx->bp_pts.ensure(2 * npairs * sizeof(cpz::ge_niels)));
+  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
+  std::vector<int32_t> ok(2 * npairs);
+  {
+    uint32_t k1[50], k2[50];
+    const bool masks = cpz::challenge_masks(k1, k2);  // the same for every pair: once, here
+    StageTimer t(ctx, 2, st);
+    CPZ_HIP(hipMemcpyAsync(ctx->bp_gh.p, pairs, npairs * 64, hipMemcpyHostToDevice, st));
+    CPZ_HIP(cpz::launch_pair_desc(static_cast<const uint32_t*>(ctx->bp_gh.p), (int)npairs, k1, k2, masks,
+                                  static_cast<cpz::PairDesc*>(ctx->bp_desc.p), static_cast<int32_t*>(ctx->bp_ok.p),
+                                  static_cast<cpz::ge_niels*>(ctx->bp_pts.p), st));
+    CPZ_HIP(hipMemcpyAsync(ok.data(), ctx->bp_ok.p, ok.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
+  CPZ_HIP(hipStreamSynchronize(st));
+  for (size_t p = 0; p < npairs; p++)
+    if (!ok[2 * p] || !ok[2 * p + 1]) return fail_pair_decode(p);
+  return CPZ_OK;
+}
+
+// The entries of a many-pair batch bucketed by pair, once per batch (the sort phase's
+// accounting: stage 3).
+int pairs_bucket(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
+  b.max_units = cpz::pair_sum_max_units(b.n, (int64_t)b.npairs);
+  CPZ_HIP(ctx->bp_list.ensure((size_t)b.n * sizeof(uint32_t)));
+  CPZ_HIP(ctx->bp_scan.ensure(3 * (b.npairs + 1) * sizeof(uint32_t)));
+  CPZ_HIP(ctx->bp_upart.ensure((size_t)b.max_units * 2 * sizeof(cpz::sc)));
+  uint32_t* scan = static_cast<uint32_t*>(ctx->bp_scan.p);
+  b.d_list = static_cast<const uint32_t*>(ctx->bp_list.p);
+  b.d_start = scan;
+  b.d_ustart = scan + (b.npairs + 1);
+  b.d_upart = static_cast<cpz::sc*>(ctx->bp_upart.p);
+  StageTimer t(ctx, 3, st);
+  CPZ_HIP(cpz::launch_pair_bucket(b.d_idx, b.n, (int)b.npairs, static_cast<uint32_t*>(ctx->bp_list.p), scan,
+                                  scan + (b.npairs + 1), scan + 2 * (b.npairs + 1), st));
+  return CPZ_OK;
+}
+
+// cpz_verify_batch_pairs_ex (max_pairs = CPZ_PAIRS_MAX) and, for more pairs than that,
+// cpz_verify_batch_pairs_many (CPZ_BATCH_PAIRS_MANY_MAX).  More than CPZ_PAIRS_MAX pairs: the
+// descriptors are built on the device, the per-pair sums come from the bucketed lists, and a
+// failing batch is bisected down to runs (CPZ_CALL_PARTITIONED is ignored: part.hip's lists hold
+// CPZ_PAIRS_MAX pairs).
+int verify_batch_pairs_impl(cpz_ctx* ctx, uint32_t flags, size_t max_pairs, const char* pairs_bound, size_t npairs,
+                            const uint8_t* pairs, size_t n, const uint32_t* pair_idx, const uint8_t* y1,
+                            const uint8_t* y2, const uint8_t* r1, const uint8_t* r2, const uint8_t* s,
+                            const uint8_t* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present,
+                            const uint8_t seed[32], uint64_t first_index, uint8_t partial_out[32], int* batch_ok,
+                            uint8_t* status_out) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+  int rc = check_npairs(npairs, max_pairs, pairs_bound);
+  if (rc) return rc;
+  if (n > CPZ_BATCH_PAIRS_MAX_PROOFS) return fail_exceeds("n", n, "CPZ_BATCH_PAIRS_MAX_PROOFS", CPZ_BATCH_PAIRS_MAX_PROOFS);
+  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !seed || !partial_out || !batch_ok)
+    return fail(CPZ_EINVAL, "null input pointer");
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  if ((rc = check_pair_indices(pair_idx, n, npairs))) return rc;  // before anything is staged
+  if ((rc = check_pairs(npairs, pairs))) return rc;
+  if (npairs == 1)
+    return cpz_verify_batch_ex(ctx, flags, pairs, pairs + 32, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present,
+                               seed, first_index, partial_out, batch_ok, status_out);
+  const bool many = npairs > CPZ_PAIRS_MAX;
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  for (auto& v : ctx->fb_stats) v = 0;
+  hipStream_t st = ctx->stream;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  std::vector<uint8_t> block;  // up to CPZ_PAIRS_MAX pairs: descriptors, then indices
+  rc = many ? pairs_setup_device(ctx, npairs, pairs, st) : pairs_setup_host(ctx, npairs, pairs, pair_idx, n, st, block);
+  if (rc) return rc;
+  // the indices (and the host-built descriptors) go to the device in one block with the rows
+  const uint8_t* host[5] = {y1, y2, r1, r2, s};
+  Staged in;
+  const void* dex = nullptr;
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, in, false, nullptr, nullptr,
+                    many ? static_cast<const void*>(pair_idx) : block.data(), many ? n * sizeof(uint32_t) : block.size(),
+                    &dex);
+  if (rc) return rc;
+  if (!dex)
+    return fail(CPZ_EHIP, many ? "internal: the pair indices were not staged"
+                               : "internal: the pair descriptors were not staged");
+  CPZ_HIP(ctx->st.ensure(n));
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  PairBatch b;
+  b.npairs = npairs;
+  b.n = (int64_t)n;
+  b.pairs = pairs;
+  b.pair_idx = pair_idx;
+  b.rows = in.rows;
+  b.cx = in.cx;
+  b.d_status = static_cast<uint8_t*>(ctx->st.p);
+  b.seed = seed;
+  b.first_index = first_index;
+  cpz::PairArgs pa;  // the table-less descriptors and the indices
+  if (many) {
+    pa.desc = b.d_desc = static_cast<cpz::PairDesc*>(ctx->bp_desc.p);
+    pa.pair_idx = static_cast<const uint32_t*>(dex);
+    b.d_full = b.d_desc;  // the leaves patch the tables of the pairs they read into these rows
+    b.room = kPairRoomMany;
+  } else {
+    pa = staged_pair_args(dex, npairs);
+  }
+  b.d_idx = pa.pair_idx;
+  if (many && (rc = pairs_bucket(ctx, b, st))) return rc;
+  {
+    const cpz::ChallengeArgs ca =
+        pairs_challenge_args(ctx, b.n, b.rows, b.cx, static_cast<uint32_t*>(ctx->c.p), b.d_status);
+    StageTimer t(ctx, 0, st);
+    CPZ_HIP(cpz::launch_challenge_pairs(ca, pa, st));
+  }
+  if ((rc = rlc_prepare_points(ctx, n, b.rows, b.d_status, seed, first_index, st, true, b.room))) return rc;
+  if ((rc = pairs_range_launch(ctx, b, 0, b.n, st))) return rc;
+  // the partial, its identity flag, the any-bad word and the statuses with one synchronisation;
+  // the caller's buffers are written only once nothing can fail before the fallback
+  uint8_t part[32];
+  int words[2] = {0, 0};
+  std::vector<uint8_t> st_host(status_out ? n : 0);
+  CPZ_HIP(hipMemcpyAsync(part, ctx->rl_msm.partial.p, 32, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipMemcpyAsync(&words[0], ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipMemcpyAsync(&words[1], static_cast<int*>(ctx->rl_flags.p) + 3, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (status_out) CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  const bool ident = words[0] != 0;
+  if (!ident && status_out) {
+    if (!many && (flags & CPZ_CALL_PARTITIONED)) {  // the caller knows its density: no bisection
+      ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
+      rc = pairs_part(ctx, b, 0, b.n, st);
+    } else {
+      ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
+      rc = many ? pairs_many_fallback(ctx, b, st) : pairs_fallback(ctx, b, st);
+    }
+    if (rc) return rc;
+    CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
     CPZ_HIP(hipStreamSynchronize(st));
-    ctx->fb_stats[5] += 1;
-    failing[k] = !ident;
-    nfail += failing[k] ? 1 : 0;
   }
-  if (2 * nfail > kFanout) return pairs_many_leaf(ctx, b, ms, lo, hi, st);  // dense failures: no pruning left
-  for (int k = 0; k < kFanout; k++) {
-    if (!failing[k]) continue;
-    if (int rc = pairs_many_fallback(ctx, b, ms, cuts[k], cuts[k + 1], st, depth + 1)) return rc;
-  }
+  std::memcpy(partial_out, part, 32);
+  *batch_ok = (ident && words[1] == 0) ? 1 : 0;
+  if (status_out) std::memcpy(status_out, st_host.data(), n);
   return CPZ_OK;
 }
 
@@ -3435,158 +3557,9 @@ int cpz_verify_batch_pairs_ex(cpz_ctx* ctx, uint32_t flags, size_t npairs, const
                               const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
                               const uint8_t* ctx_present, const uint8_t seed[32], uint64_t first_index,
                               uint8_t partial_out[32], int* batch_ok, uint8_t* status_out) {
-  if (!ctx) return fail(CPZ_EINVAL, "null context");
-  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
-  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
-  if (npairs > CPZ_PAIRS_MAX)
-    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
-                                std::to_string(CPZ_PAIRS_MAX) + ")");
-  if (n > CPZ_BATCH_PAIRS_MAX_PROOFS)
-    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_BATCH_PAIRS_MAX_PROOFS (" +
-                                std::to_string(CPZ_BATCH_PAIRS_MAX_PROOFS) + ")");
-  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !seed || !partial_out || !batch_ok)
-    return fail(CPZ_EINVAL, "null input pointer");
-  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
-  // the kernels trust the indices: checked here, before anything is staged
-  for (size_t i = 0; i < n; i++)
-    if (pair_idx[i] >= npairs)
-      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
-                                  " is not below npairs (" + std::to_string(npairs) + ")");
-  // Parameters::with_generators (gadgets.rs:77-103) for every pair
-  static const uint8_t zero[32] = {0};
-  for (size_t p = 0; p < npairs; p++) {
-    const uint8_t *g = pairs + 64 * p, *h = g + 32;
-    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
-    if (std::memcmp(g, h, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
-  }
-  if (npairs == 1)
-    return cpz_verify_batch_ex(ctx, flags, pairs, pairs + 32, n, y1, y2, r1, r2, s, ctx_bytes, ctx_off, ctx_present,
-                               seed, first_index, partial_out, batch_ok, status_out);
-  CallLock lock(ctx, flags);
-  CPZ_HIP(hipSetDevice(ctx->device));
-  for (auto& v : ctx->fb_stats) v = 0;
-  hipStream_t st = ctx->stream;
-  int rc = order_after_last(ctx, st);
-  if (rc) return rc;
-  // Per-pair set-up, no table: one launch for the snapshots and the pairs' Niels points, one
-  // copy back for the snapshots and decode flags (timed inside stage 2).
-  CPZ_HIP(ctx->bp_gh.ensure(npairs * 64));
-  CPZ_HIP(ctx->bp_setup.ensure(npairs * sizeof(cpz::PairSetup)));
-  CPZ_HIP(ctx->bp_pts.ensure(2 * npairs * sizeof(cpz::ge_niels)));
-  std::vector<cpz::PairSetup> setup(npairs);
-  {
-    StageTimer t(ctx, 2, st);
-    CPZ_HIP(hipMemcpyAsync(ctx->bp_gh.p, pairs, npairs * 64, hipMemcpyHostToDevice, st));
-    CPZ_HIP(cpz::launch_pair_setup(static_cast<const uint32_t*>(ctx->bp_gh.p), (int)npairs,
-                                   static_cast<cpz::PairSetup*>(ctx->bp_setup.p),
-                                   static_cast<cpz::ge_niels*>(ctx->bp_pts.p), st));
-    CPZ_HIP(hipMemcpyAsync(setup.data(), ctx->bp_setup.p, npairs * sizeof(cpz::PairSetup), hipMemcpyDeviceToHost, st));
-  }
-  CPZ_HIP(hipStreamSynchronize(st));
-  for (size_t p = 0; p < npairs; p++)
-    if (!setup[p].ok[0] || !setup[p].ok[1])
-      return fail(CPZ_EGENERATOR,
-                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
-  // The descriptors (null tables) with the host-derived fixed-schedule masks, and the indices,
-  // go to the device in one block with the rows (stage_inputs' extra).
-  std::vector<uint8_t> extra(npairs * sizeof(cpz::PairDesc) + n * sizeof(uint32_t));
-  {
-    uint32_t k1[50], k2[50];
-    const bool masks = cpz::challenge_masks(k1, k2);
-    for (size_t p = 0; p < npairs; p++) {
-      cpz::PairDesc d{};
-      std::memcpy(d.prefix, setup[p].prefix, sizeof(d.prefix));
-      words_from_bytes(d.gh_words, pairs + 64 * p, pairs + 64 * p + 32);
-      d.fast_noctx = masks && cpz::challenge_prefix_is_fixed(d.prefix[1]) ? 1 : 0;
-      std::memcpy(d.k1, k1, sizeof(d.k1));
-      std::memcpy(d.k2, k2, sizeof(d.k2));
-      d.fast_ctx32 = cpz::challenge_prefix_is_ctx32(d.prefix[0]) &&
-                             cpz::challenge_masks_ctx32(d.c32, d.gh_words, d.gh_words + 8)
-                         ? 1
-                         : 0;
-      std::memcpy(extra.data() + p * sizeof(cpz::PairDesc), &d, sizeof(d));
-    }
-  }
-  std::memcpy(extra.data() + npairs * sizeof(cpz::PairDesc), pair_idx, n * sizeof(uint32_t));
-  const uint8_t* host[5] = {y1, y2, r1, r2, s};
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
-  const void* dex = nullptr;
-  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, false, nullptr, nullptr,
-                    extra.data(), extra.size(), &dex);
-  if (rc) return rc;
-  if (!dex) return fail(CPZ_EHIP, "internal: the pair descriptors were not staged");
-  CPZ_HIP(ctx->st.ensure(n));
-  CPZ_HIP(ctx->c.ensure(n * 32));
-  PairBatch b;
-  b.npairs = npairs;
-  b.n = (int64_t)n;
-  b.pairs = pairs;
-  b.pair_idx = pair_idx;
-  for (int k = 0; k < 5; k++) b.rows[k] = dev[k];
-  b.cb = dcb;
-  b.co = dco;
-  b.cp = dcp;
-  b.d_idx = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(dex) + npairs * sizeof(cpz::PairDesc));
-  b.d_status = static_cast<uint8_t*>(ctx->st.p);
-  b.seed = seed;
-  b.first_index = first_index;
-  {
-    cpz::ChallengeArgs ca{};
-    ca.eq_only = ctx->call_eq ? 1 : 0;
-    ca.n = (int64_t)n;
-    ca.y1 = static_cast<const uint32_t*>(dev[0]);
-    ca.y2 = static_cast<const uint32_t*>(dev[1]);
-    ca.r1 = static_cast<const uint32_t*>(dev[2]);
-    ca.r2 = static_cast<const uint32_t*>(dev[3]);
-    ca.s = static_cast<const uint32_t*>(dev[4]);
-    ca.ctx_bytes = static_cast<const uint8_t*>(dcb);
-    ca.ctx_off = dco;
-    ca.ctx_present = dcp;
-    ca.prefix = nullptr;  // per pair: PairDesc
-    ca.c_out = static_cast<uint32_t*>(ctx->c.p);
-    ca.status_out = b.d_status;
-    cpz::PairArgs pa;
-    pa.desc = static_cast<const cpz::PairDesc*>(dex);
-    pa.pair_idx = b.d_idx;
-    StageTimer t(ctx, 0, st);
-    CPZ_HIP(cpz::launch_challenge_pairs(ca, pa, st));
-  }
-  if ((rc = rlc_prepare_points(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], b.d_status, seed, first_index, st, true,
-                               b.room)))
-    return rc;
-  if ((rc = pairs_range_launch(ctx, b, 0, (int64_t)n, st))) return rc;
-  // the partial, its identity flag, the any-bad word and the statuses with one synchronisation;
-  // the caller's buffers are written only once nothing can fail before the fallback
-  uint8_t part[32];
-  int words[2] = {0, 0};
-  std::vector<uint8_t> st_host(status_out ? n : 0);
-  CPZ_HIP(hipMemcpyAsync(part, ctx->rl_msm.partial.p, 32, hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipMemcpyAsync(&words[0], ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipMemcpyAsync(&words[1], static_cast<int*>(ctx->rl_flags.p) + 3, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (status_out) CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipStreamSynchronize(st));
-  const bool ident = words[0] != 0;
-  if (!ident && status_out) {
-    if (flags & CPZ_CALL_PARTITIONED) {  // the caller knows its density: no bisection
-      ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
-      rc = pairs_part(ctx, b, 0, (int64_t)n, st);
-    } else {
-      ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
-      rc = pairs_fallback(ctx, b, 0, (int64_t)n, st, 0);
-    }
-    if (rc) return rc;
-    CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
-    CPZ_HIP(hipStreamSynchronize(st));
-  }
-  std::memcpy(partial_out, part, 32);
-  *batch_ok = (ident && words[1] == 0) ? 1 : 0;
-  if (status_out) std::memcpy(status_out, st_host.data(), n);
-  return CPZ_OK;
+  return verify_batch_pairs_impl(ctx, flags, CPZ_PAIRS_MAX, "CPZ_PAIRS_MAX", npairs, pairs, n, pair_idx, y1, y2, r1, r2,
+                                 s, ctx_bytes, ctx_off, ctx_present, seed, first_index, partial_out, batch_ok,
+                                 status_out);
 }
 
 int cpz_verify_batch_pairs_many(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
@@ -3595,156 +3568,11 @@ int cpz_verify_batch_pairs_many(cpz_ctx* ctx, uint32_t flags, size_t npairs, con
                                 const uint8_t* ctx_present, const uint8_t seed[32], uint64_t first_index,
                                 uint8_t partial_out[32], int* batch_ok, uint8_t* status_out) {
   // up to CPZ_PAIRS_MAX pairs this is cpz_verify_batch_pairs_ex itself: same route, same timing
-  if (npairs <= CPZ_PAIRS_MAX)
-    return cpz_verify_batch_pairs_ex(ctx, flags, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, ctx_bytes, ctx_off,
-                                     ctx_present, seed, first_index, partial_out, batch_ok, status_out);
-  // its checks, in its order and wording
-  if (!ctx) return fail(CPZ_EINVAL, "null context");
-  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
-  if (npairs > CPZ_BATCH_PAIRS_MANY_MAX)
-    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_BATCH_PAIRS_MANY_MAX (" +
-                                std::to_string(CPZ_BATCH_PAIRS_MANY_MAX) + ")");
-  if (n > CPZ_BATCH_PAIRS_MAX_PROOFS)
-    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_BATCH_PAIRS_MAX_PROOFS (" +
-                                std::to_string(CPZ_BATCH_PAIRS_MAX_PROOFS) + ")");
-  if (!pairs || !pair_idx || !y1 || !y2 || !r1 || !r2 || !s || !seed || !partial_out || !batch_ok)
-    return fail(CPZ_EINVAL, "null input pointer");
-  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
-  for (size_t i = 0; i < n; i++)
-    if (pair_idx[i] >= npairs)
-      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
-                                  " is not below npairs (" + std::to_string(npairs) + ")");
-  static const uint8_t zero[32] = {0};
-  for (size_t p = 0; p < npairs; p++) {
-    const uint8_t *g = pairs + 64 * p, *h = g + 32;
-    if (std::memcmp(g, zero, 32) == 0 || std::memcmp(h, zero, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generator cannot be identity");
-    if (std::memcmp(g, h, 32) == 0)
-      return fail(CPZ_EGENERATOR, "pair " + std::to_string(p) + ": generators g and h must be different");
-  }
-  CallLock lock(ctx, flags);
-  CPZ_HIP(hipSetDevice(ctx->device));
-  for (auto& v : ctx->fb_stats) v = 0;
-  hipStream_t st = ctx->stream;
-  int rc = order_after_last(ctx, st);
-  if (rc) return rc;
-  // Per-pair set-up on the device: the table-less descriptor rows, the pairs' Niels points and
-  // the decode flags, which alone come back (timed inside stage 2, as k_pair_setup is).
-  CPZ_HIP(ctx->bp_gh.ensure(npairs * 64));
-  CPZ_HIP(ctx->bp_ok.ensure(npairs * 2 * sizeof(int32_t)));
-  CPZ_HIP(ctx->bp_pts.ensure(2 * npairs * sizeof(cpz::ge_niels)));
-  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
-  std::vector<int32_t> ok(2 * npairs);
-  {
-    uint32_t k1[50], k2[50];
-    const bool masks = cpz::challenge_masks(k1, k2);  // the same for every pair: once, here
-    StageTimer t(ctx, 2, st);
-    CPZ_HIP(hipMemcpyAsync(ctx->bp_gh.p, pairs, npairs * 64, hipMemcpyHostToDevice, st));
-    CPZ_HIP(cpz::launch_pair_desc(static_cast<const uint32_t*>(ctx->bp_gh.p), (int)npairs, k1, k2, masks,
-                                  static_cast<cpz::PairDesc*>(ctx->bp_desc.p), static_cast<int32_t*>(ctx->bp_ok.p),
-                                  static_cast<cpz::ge_niels*>(ctx->bp_pts.p), st));
-    CPZ_HIP(hipMemcpyAsync(ok.data(), ctx->bp_ok.p, ok.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  }
-  CPZ_HIP(hipStreamSynchronize(st));
-  for (size_t p = 0; p < npairs; p++)
-    if (!ok[2 * p] || !ok[2 * p + 1])
-      return fail(CPZ_EGENERATOR,
-                  "pair " + std::to_string(p) + ": generator encoding does not decode to a ristretto255 point");
-  // the indices go to the device in one block with the rows (stage_inputs' extra)
-  const uint8_t* host[5] = {y1, y2, r1, r2, s};
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
-  const void* dex = nullptr;
-  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp, false, nullptr, nullptr,
-                    pair_idx, n * sizeof(uint32_t), &dex);
-  if (rc) return rc;
-  if (!dex) return fail(CPZ_EHIP, "internal: the pair indices were not staged");
-  CPZ_HIP(ctx->st.ensure(n));
-  CPZ_HIP(ctx->c.ensure(n * 32));
-  PairBatch b;
-  b.npairs = npairs;
-  b.n = (int64_t)n;
-  b.pairs = pairs;
-  b.pair_idx = pair_idx;
-  for (int k = 0; k < 5; k++) b.rows[k] = dev[k];
-  b.cb = dcb;
-  b.co = dco;
-  b.cp = dcp;
-  b.d_idx = static_cast<const uint32_t*>(dex);
-  b.d_status = static_cast<uint8_t*>(ctx->st.p);
-  b.d_desc = static_cast<cpz::PairDesc*>(ctx->bp_desc.p);
-  b.d_full = b.d_desc;  // the leaves patch the tables of the pairs they read into these rows
-  b.seed = seed;
-  b.first_index = first_index;
-  b.room = kPairRoomMany;
-  // the entries bucketed by pair, once per batch (the sort phase's accounting: stage 3)
-  b.max_units = cpz::pair_sum_max_units((int64_t)n, (int64_t)npairs);
-  CPZ_HIP(ctx->bp_list.ensure(n * sizeof(uint32_t)));
-  CPZ_HIP(ctx->bp_scan.ensure(3 * (npairs + 1) * sizeof(uint32_t)));
-  CPZ_HIP(ctx->bp_upart.ensure((size_t)b.max_units * 2 * sizeof(cpz::sc)));
-  {
-    uint32_t* scan = static_cast<uint32_t*>(ctx->bp_scan.p);
-    b.d_list = static_cast<const uint32_t*>(ctx->bp_list.p);
-    b.d_start = scan;
-    b.d_ustart = scan + (npairs + 1);
-    b.d_upart = static_cast<cpz::sc*>(ctx->bp_upart.p);
-    StageTimer t(ctx, 3, st);
-    CPZ_HIP(cpz::launch_pair_bucket(b.d_idx, (int64_t)n, (int)npairs, static_cast<uint32_t*>(ctx->bp_list.p), scan,
-                                    scan + (npairs + 1), scan + 2 * (npairs + 1), st));
-  }
-  {
-    cpz::ChallengeArgs ca{};
-    ca.eq_only = ctx->call_eq ? 1 : 0;
-    ca.n = (int64_t)n;
-    ca.y1 = static_cast<const uint32_t*>(dev[0]);
-    ca.y2 = static_cast<const uint32_t*>(dev[1]);
-    ca.r1 = static_cast<const uint32_t*>(dev[2]);
-    ca.r2 = static_cast<const uint32_t*>(dev[3]);
-    ca.s = static_cast<const uint32_t*>(dev[4]);
-    ca.ctx_bytes = static_cast<const uint8_t*>(dcb);
-    ca.ctx_off = dco;
-    ca.ctx_present = dcp;
-    ca.prefix = nullptr;  // per pair: PairDesc
-    ca.c_out = static_cast<uint32_t*>(ctx->c.p);
-    ca.status_out = b.d_status;
-    cpz::PairArgs pa;
-    pa.desc = b.d_desc;
-    pa.pair_idx = b.d_idx;
-    StageTimer t(ctx, 0, st);
-    CPZ_HIP(cpz::launch_challenge_pairs(ca, pa, st));
-  }
-  if ((rc = rlc_prepare_points(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], b.d_status, seed, first_index, st, true,
-                               b.room)))
-    return rc;
-  if ((rc = pairs_range_launch(ctx, b, 0, (int64_t)n, st))) return rc;
-  uint8_t part[32];
-  int words[2] = {0, 0};
-  std::vector<uint8_t> st_host(status_out ? n : 0);
-  CPZ_HIP(hipMemcpyAsync(part, ctx->rl_msm.partial.p, 32, hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipMemcpyAsync(&words[0], ctx->rl_msm.flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipMemcpyAsync(&words[1], static_cast<int*>(ctx->rl_flags.p) + 3, sizeof(int), hipMemcpyDeviceToHost, st));
-  if (status_out) CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
-  CPZ_HIP(hipStreamSynchronize(st));
-  const bool ident = words[0] != 0;
-  if (!ident && status_out) {
-    // bisection, then runs; CPZ_CALL_PARTITIONED is ignored (part.hip's lists hold CPZ_PAIRS_MAX pairs)
-    ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
-    ManyRuns ms;
-    ms.stamp.assign(npairs, 0);
-    ms.rows.resize(64 * CPZ_PAIRS_MAX);
-    ms.full.resize(CPZ_PAIRS_MAX);
-    const char* deep = std::getenv("CPZ_PAIRS_MANY_DEEP");
-    ms.deep = !(deep && deep[0] == '0');
-    if ((rc = pairs_many_fallback(ctx, b, ms, 0, (int64_t)n, st, 0))) return rc;
-    CPZ_HIP(hipMemcpyAsync(st_host.data(), b.d_status, n, hipMemcpyDeviceToHost, st));
-    CPZ_HIP(hipStreamSynchronize(st));
-  }
-  std::memcpy(partial_out, part, 32);
-  *batch_ok = (ident && words[1] == 0) ? 1 : 0;
-  if (status_out) std::memcpy(status_out, st_host.data(), n);
-  return CPZ_OK;
+  const bool many = npairs > CPZ_PAIRS_MAX;
+  return verify_batch_pairs_impl(ctx, flags, many ? CPZ_BATCH_PAIRS_MANY_MAX : CPZ_PAIRS_MAX,
+                                 many ? "CPZ_BATCH_PAIRS_MANY_MAX" : "CPZ_PAIRS_MAX", npairs, pairs, n, pair_idx, y1, y2,
+                                 r1, r2, s, ctx_bytes, ctx_off, ctx_present, seed, first_index, partial_out, batch_ok,
+                                 status_out);
 }
 
 int cpz_challenges(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const uint8_t* y1,
@@ -3759,28 +3587,12 @@ int cpz_challenges(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_
   if (rc) return rc;
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
   const uint8_t* host[5] = {y1, y2, r1, r2, nullptr};
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
-  rc = stage_inputs(ctx, n, host, 4, ctx_bytes, ctx_off, ctx_present, dev, &dcb, &dco, &dcp);
+  Staged in;  // no s: no response status either
+  rc = stage_inputs(ctx, n, host, 4, ctx_bytes, ctx_off, ctx_present, in);
   if (rc) return rc;
   CPZ_HIP(ctx->c.ensure(n * 32));
-  cpz::ChallengeArgs ca;
-  set_challenge_schedules(ctx, ca);
-  ca.n = (int64_t)n;
-  words_from_bytes(ca.gh_words, ctx->gs->gh, ctx->gs->gh + 32);
-  ca.y1 = static_cast<const uint32_t*>(dev[0]);
-  ca.y2 = static_cast<const uint32_t*>(dev[1]);
-  ca.r1 = static_cast<const uint32_t*>(dev[2]);
-  ca.r2 = static_cast<const uint32_t*>(dev[3]);
-  ca.s = nullptr;
-  ca.ctx_bytes = static_cast<const uint8_t*>(dcb);
-  ca.ctx_off = dco;
-  ca.ctx_present = dcp;
-  ca.prefix = static_cast<const cpz::StrobeSnap*>(ctx->gs->prefix.p);
-  ca.c_out = static_cast<uint32_t*>(ctx->c.p);
-  ca.status_out = nullptr;
+  const cpz::ChallengeArgs ca =
+      challenge_args(ctx, (int64_t)n, in.rows, in.cx, static_cast<uint32_t*>(ctx->c.p), nullptr);
   CPZ_HIP(cpz::launch_challenge(ca, ctx->stream));
   CPZ_HIP(hipMemcpyAsync(c_out, ctx->c.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
   CPZ_HIP(hipStreamSynchronize(ctx->stream));
@@ -3855,50 +3667,46 @@ int cpz_parse_proofs(cpz_ctx* ctx, size_t n, const uint8_t* blob, const uint64_t
 
 namespace {
 
+// The prover's five output rows on the device.
+struct OutRows {
+  void *y1, *y2, *r1, *r2, *s;
+};
+
+// ProveArgs of n proofs from the witnesses d_x and nonces d_k (null: synthetic, from the seeds the
+// caller then sets) into `out`, the challenges in ctx->c; no comb.
+cpz::ProveArgs prove_args(const cpz_ctx* ctx, size_t n, const void* d_x, const void* d_k, const OutRows& out) {
+  cpz::ProveArgs pa{};
+  pa.n = (int64_t)n;
+  pa.x_in = static_cast<const uint32_t*>(d_x);
+  pa.k_in = static_cast<const uint32_t*>(d_k);
+  pa.y1 = static_cast<uint32_t*>(out.y1);
+  pa.y2 = static_cast<uint32_t*>(out.y2);
+  pa.r1 = static_cast<uint32_t*>(out.r1);
+  pa.r2 = static_cast<uint32_t*>(out.r2);
+  pa.c = static_cast<const uint32_t*>(ctx->c.p);
+  pa.s_out = static_cast<uint32_t*>(out.s);
+  return pa;
+}
+
 // Prover::prove_with_transcript (prover/mod.rs:86-131) for n proofs on the device: x_i, k_i
 // from the caller (d_x / d_k, mod l) or, when those are null, from ChaCha20(seed, first_index
 // + i) (synthetic inputs).  y = x g, x h (gadgets.rs:217-221); r = k g, k h (commit,
 // :115-121); c from the transcript (contexts as in verify); s = k + c x (respond, :126-131).
 int prove_impl(cpz_ctx* ctx, size_t n, uint64_t first_index, const uint8_t* seed_x, const uint8_t* seed_k,
-               const void* d_x, const void* d_k, const void* d_ctx_bytes, const uint64_t* d_ctx_off,
-               const uint8_t* d_ctx_present, void* d_y1, void* d_y2, void* d_r1, void* d_r2, void* d_s,
-               hipStream_t st) {
+               const void* d_x, const void* d_k, const Ctxs& cx, const OutRows& out, hipStream_t st) {
   CPZ_HIP(ctx->c.ensure(n * 32));
-  cpz::ProveArgs pa;
-  pa.n = (int64_t)n;
+  cpz::ProveArgs pa = prove_args(ctx, n, d_x, d_k, out);
   pa.first_index = first_index;
-  std::memset(pa.seed_x, 0, 32);
-  std::memset(pa.seed_k, 0, 32);
   if (seed_x) std::memcpy(pa.seed_x, seed_x, 32);
   if (seed_k) std::memcpy(pa.seed_k, seed_k, 32);
-  pa.x_in = static_cast<const uint32_t*>(d_x);
-  pa.k_in = static_cast<const uint32_t*>(d_k);
   pa.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
-  pa.y1 = static_cast<uint32_t*>(d_y1);
-  pa.y2 = static_cast<uint32_t*>(d_y2);
-  pa.r1 = static_cast<uint32_t*>(d_r1);
-  pa.r2 = static_cast<uint32_t*>(d_r2);
-  pa.c = static_cast<const uint32_t*>(ctx->c.p);
-  pa.s_out = static_cast<uint32_t*>(d_s);
   {
     StageTimer t(ctx, 6, st);
     CPZ_HIP(cpz::launch_prove_points(pa, st));
   }
-  cpz::ChallengeArgs ca;
-  set_challenge_schedules(ctx, ca);
-  ca.n = (int64_t)n;
-  words_from_bytes(ca.gh_words, ctx->gs->gh, ctx->gs->gh + 32);
-  ca.y1 = pa.y1;
-  ca.y2 = pa.y2;
-  ca.r1 = pa.r1;
-  ca.r2 = pa.r2;
-  ca.s = nullptr;
-  ca.ctx_bytes = static_cast<const uint8_t*>(d_ctx_bytes);
-  ca.ctx_off = d_ctx_off;
-  ca.ctx_present = d_ctx_present;
-  ca.prefix = static_cast<const cpz::StrobeSnap*>(ctx->gs->prefix.p);
-  ca.c_out = static_cast<uint32_t*>(ctx->c.p);
-  ca.status_out = nullptr;
+  // (no response yet: no status either)
+  const cpz::ChallengeArgs ca = challenge_args(ctx, (int64_t)n, Rows(pa.y1, pa.y2, pa.r1, pa.r2, nullptr), cx,
+                                               static_cast<uint32_t*>(ctx->c.p), nullptr);
   StageTimer t(ctx, 6, st);
   CPZ_HIP(cpz::launch_challenge(ca, st));
   CPZ_HIP(cpz::launch_prove_response(pa, st));
@@ -3922,12 +3730,9 @@ int prove_host(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n,
   int rc = ensure_generators(ctx, g, h);
   if (rc) return rc;
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
-  const void* dcb = nullptr;
-  const uint64_t* dco = nullptr;
-  const uint8_t* dcp = nullptr;
-  const void* unused[5];
+  Staged in;  // the contexts alone
   const uint8_t* none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  rc = stage_inputs(ctx, n, none, 0, ctx_bytes, ctx_off, ctx_present, unused, &dcb, &dco, &dcp);
+  rc = stage_inputs(ctx, n, none, 0, ctx_bytes, ctx_off, ctx_present, in);
   if (rc) return rc;
   for (int q = 0; q < 5; q++) CPZ_HIP(ctx->in[q].ensure(n * 32));
   const void* dx = nullptr;
@@ -3940,8 +3745,8 @@ int prove_host(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n,
     dx = ctx->in[5].p;
     dk = ctx->in[6].p;
   }
-  rc = prove_impl(ctx, n, first_index, seed_x, seed_k, dx, dk, dcb, dco, dcp, ctx->in[0].p, ctx->in[1].p,
-                  ctx->in[2].p, ctx->in[3].p, ctx->in[4].p, ctx->stream);
+  rc = prove_impl(ctx, n, first_index, seed_x, seed_k, dx, dk, in.cx,
+                  OutRows{ctx->in[0].p, ctx->in[1].p, ctx->in[2].p, ctx->in[3].p, ctx->in[4].p}, ctx->stream);
   if (rc) return rc;
   uint8_t* outs[5] = {y1, y2, r1, r2, s};
   for (int q = 0; q < 5; q++)
@@ -3951,29 +3756,12 @@ int prove_host(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n,
 }
 
 // Verifier::verify_response (verifier/mod.rs:144-171) with caller challenges c (device rows).
-int verify_response_impl(cpz_ctx* ctx, size_t n, const void* y1, const void* y2, const void* r1, const void* r2,
-                         const void* s, const void* c, uint8_t* status, hipStream_t st) {
+int verify_response_impl(cpz_ctx* ctx, size_t n, const Rows& rows, const void* c, uint8_t* status, hipStream_t st) {
   CPZ_HIP(ctx->c.ensure(n * 32));
-  CPZ_HIP(cpz::launch_response_prep((int64_t)n, static_cast<const uint32_t*>(s), static_cast<const uint32_t*>(c),
+  CPZ_HIP(cpz::launch_response_prep((int64_t)n, rows.s, static_cast<const uint32_t*>(c),
                                     static_cast<uint32_t*>(ctx->c.p), status, ctx->call_eq ? 1 : 0, st));
   cpz::VerifyArgs va;
-  va.n = (int64_t)n;
-  va.y1 = static_cast<const uint32_t*>(y1);
-  va.y2 = static_cast<const uint32_t*>(y2);
-  va.r1 = static_cast<const uint32_t*>(r1);
-  va.r2 = static_cast<const uint32_t*>(r2);
-  va.s = static_cast<const uint32_t*>(s);
-  va.c = static_cast<const uint32_t*>(ctx->c.p);
-  va.status = status;
-  va.comb = static_cast<const cpz::ge_niels*>(ctx->gs->comb.p);
-  if (!ctx->gs->full) {  // a light set: variable-base generators (ensure_generators, n <= var_base_max)
-    if ((int64_t)n > var_base_max(ctx)) return fail(CPZ_EINVAL, "internal: variable-base call above var_base_max");
-    va.comb = nullptr;
-    va.vtab = static_cast<const cpz::ge_niels*>(ctx->gs->tab.p);
-    va.vtab16 = static_cast<const int32_t*>(ctx->gs->tab16.p);
-  }
-  va.scratch = nullptr;  // set per launch
-  va.eq_only = ctx->call_eq ? 1 : 0;
+  if (int rc = pair_verify_args(ctx, (int64_t)n, rows, static_cast<const uint32_t*>(ctx->c.p), status, va)) return rc;
   StageTimer span(ctx, 5, st);
   return launch_verify_chunks(ctx, va, 1, st, nullptr, true);
 }
@@ -3985,13 +3773,8 @@ int prove_pairs_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, s
                             const void* const rows[7]) {
   if (!ctx) return fail(CPZ_EINVAL, "null context");
   if (n == 0) return fail(CPZ_EEMPTY, "empty input");
-  if (npairs == 0) return fail(CPZ_EINVAL, "npairs is 0: a mixed-pair call needs at least one (g, h) pair");
-  if (npairs > CPZ_PAIRS_MAX)
-    return fail(CPZ_EINVAL, "npairs " + std::to_string(npairs) + " exceeds CPZ_PAIRS_MAX (" +
-                                std::to_string(CPZ_PAIRS_MAX) + ")");
-  if (n > CPZ_PROVE_PAIRS_MAX_PROOFS)
-    return fail(CPZ_EINVAL, "n " + std::to_string(n) + " exceeds CPZ_PROVE_PAIRS_MAX_PROOFS (" +
-                                std::to_string(CPZ_PROVE_PAIRS_MAX_PROOFS) + ")");
+  if (int rc = check_npairs(npairs)) return rc;
+  if (n > CPZ_PROVE_PAIRS_MAX_PROOFS) return fail_exceeds("n", n, "CPZ_PROVE_PAIRS_MAX_PROOFS", CPZ_PROVE_PAIRS_MAX_PROOFS);
   if (!pairs || !pair_idx) return fail(CPZ_EINVAL, "null input pointer");
   for (int q = 0; q < 7; q++)
     if (!rows[q]) return fail(CPZ_EINVAL, "null input or output pointer");
@@ -4003,23 +3786,9 @@ int prove_pairs_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, s
 // no comb, no table slab, so one launch for any n), the challenges from k_challenge_pairs with
 // each pair's transcript prefix, the responses from k_prove_response.
 int prove_pairs_impl(cpz_ctx* ctx, size_t n, const cpz::PairDesc* d_desc, const uint32_t* d_idx, const void* d_x,
-                     const void* d_k, const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
-                     void* d_y1, void* d_y2, void* d_r1, void* d_r2, void* d_s, hipStream_t st) {
+                     const void* d_k, const Ctxs& cx, const OutRows& out, hipStream_t st) {
   CPZ_HIP(ctx->c.ensure(n * 32));
-  cpz::ProveArgs pa;
-  pa.n = (int64_t)n;
-  pa.first_index = 0;
-  std::memset(pa.seed_x, 0, 32);
-  std::memset(pa.seed_k, 0, 32);
-  pa.x_in = static_cast<const uint32_t*>(d_x);
-  pa.k_in = static_cast<const uint32_t*>(d_k);
-  pa.comb = nullptr;  // unused: the pairs' Niels tables
-  pa.y1 = static_cast<uint32_t*>(d_y1);
-  pa.y2 = static_cast<uint32_t*>(d_y2);
-  pa.r1 = static_cast<uint32_t*>(d_r1);
-  pa.r2 = static_cast<uint32_t*>(d_r2);
-  pa.c = static_cast<const uint32_t*>(ctx->c.p);
-  pa.s_out = static_cast<uint32_t*>(d_s);
+  const cpz::ProveArgs pa = prove_args(ctx, n, d_x, d_k, out);  // (no comb: the pairs' Niels tables)
   cpz::PairArgs pr;
   pr.desc = d_desc;
   pr.pair_idx = d_idx;
@@ -4027,19 +3796,10 @@ int prove_pairs_impl(cpz_ctx* ctx, size_t n, const cpz::PairDesc* d_desc, const 
     StageTimer t(ctx, 6, st);
     CPZ_HIP(cpz::launch_prove_points_pairs(pa, pr, st));
   }
-  cpz::ChallengeArgs ca{};
-  ca.n = (int64_t)n;
-  ca.y1 = pa.y1;
-  ca.y2 = pa.y2;
-  ca.r1 = pa.r1;
-  ca.r2 = pa.r2;
-  ca.s = nullptr;  // no response yet: no status either
-  ca.ctx_bytes = static_cast<const uint8_t*>(d_ctx_bytes);
-  ca.ctx_off = d_ctx_off;
-  ca.ctx_present = d_ctx_off ? d_ctx_present : nullptr;
-  ca.prefix = nullptr;  // per pair: PairDesc
-  ca.c_out = static_cast<uint32_t*>(ctx->c.p);
-  ca.status_out = nullptr;
+  // (no response yet: no status either)
+  const cpz::ChallengeArgs ca =
+      pairs_challenge_args(ctx, (int64_t)n, Rows(pa.y1, pa.y2, pa.r1, pa.r2, nullptr),
+                           Ctxs(cx.bytes, cx.off, cx.off ? cx.present : nullptr), static_cast<uint32_t*>(ctx->c.p), nullptr);
   StageTimer t(ctx, 6, st);
   CPZ_HIP(cpz::launch_challenge_pairs(ca, pr, st));
   CPZ_HIP(cpz::launch_prove_response(pa, st));
@@ -4059,15 +3819,15 @@ int cpz_prove_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], siz
   for (const void* p : rows)
     if (!p) return fail(CPZ_EINVAL, "null input or output pointer");
   if (!rows_aligned(rows, 7)) return fail(CPZ_EINVAL, "device rows must be 16-byte aligned");
-  if (d_ctx_off && !d_ctx_bytes) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  if (int rc = check_contexts(d_ctx_bytes, d_ctx_off, n, true)) return rc;
   CallLock lock(ctx);
   CPZ_HIP(hipSetDevice(ctx->device));
   int rc = ensure_generators(ctx, g, h);
   if (rc) return rc;
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   if ((rc = order_after_last(ctx, st))) return rc;
-  rc = prove_impl(ctx, n, 0, nullptr, nullptr, d_x, d_k, d_ctx_bytes, d_ctx_off, d_ctx_present, d_y1, d_y2, d_r1,
-                  d_r2, d_s, st);
+  rc = prove_impl(ctx, n, 0, nullptr, nullptr, d_x, d_k, Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present),
+                  OutRows{d_y1, d_y2, d_r1, d_r2, d_s}, st);
   if (rc) return rc;
   return record_last(ctx, st);
 }
@@ -4078,7 +3838,7 @@ int cpz_prove(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, 
   if (!ctx || !g || !h) return fail(CPZ_EINVAL, "null context or generators");
   if (n == 0) return fail(CPZ_EEMPTY, "empty input");
   if (!x || !k || !y1 || !y2 || !r1 || !r2 || !s) return fail(CPZ_EINVAL, "null input or output pointer");
-  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  if (int rc = check_contexts(ctx_bytes, ctx_off, n)) return rc;
   return prove_host(ctx, g, h, n, 0, nullptr, nullptr, x, k, ctx_bytes, ctx_off, ctx_present, y1, y2, r1, r2, s);
 }
 
@@ -4089,24 +3849,18 @@ int cpz_prove_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n,
   const void* rows[7] = {x, k, y1, y2, r1, r2, s};
   int rc = prove_pairs_head_checks(ctx, npairs, pairs, n, pair_idx, rows);
   if (rc) return rc;
-  if (ctx_off && !ctx_bytes && ctx_off[n] != ctx_off[0]) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
-  for (size_t i = 0; i < n; i++)
-    if (pair_idx[i] >= npairs)
-      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(i) + "] = " + std::to_string(pair_idx[i]) +
-                                  " is not below npairs (" + std::to_string(npairs) + ")");
-  if ((rc = pairs_bulk_generator_checks(ctx, 0, npairs, pairs))) return rc;
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  if ((rc = check_pair_indices(pair_idx, n, npairs))) return rc;
+  if ((rc = check_pairs_decode(ctx, 0, npairs, pairs))) return rc;
   CallLock lock(ctx);
   CPZ_HIP(hipSetDevice(ctx->device));
   // every pair resident at once (light sets unless a full one is cached: no comb for any npairs)
   std::vector<cpz::PairDesc> desc(npairs);
-  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
+  if ((rc = load_pairs(ctx, npairs, pairs, desc.data(), true, nullptr))) return rc;
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
-  const void* dcb = nullptr;
-  const uint64_t* dco = nullptr;
-  const uint8_t* dcp = nullptr;
-  const void* unused[5];
+  Staged in;  // the contexts alone
   const uint8_t* none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  rc = stage_inputs(ctx, n, none, 0, ctx_bytes, ctx_off, ctx_present, unused, &dcb, &dco, &dcp);
+  rc = stage_inputs(ctx, n, none, 0, ctx_bytes, ctx_off, ctx_present, in);
   if (rc) return rc;
   for (int q = 0; q < 7; q++) CPZ_HIP(ctx->in[q].ensure(n * 32));
   CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
@@ -4118,8 +3872,8 @@ int cpz_prove_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n,
   CPZ_HIP(hipMemcpyAsync(ctx->in[6].p, k, n * 32, hipMemcpyHostToDevice, ctx->stream));
   CPZ_HIP(hipStreamSynchronize(ctx->stream));  // pageable sources: read before `desc` goes
   rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p),
-                        static_cast<const uint32_t*>(ctx->pp_idx.p), ctx->in[5].p, ctx->in[6].p, dcb, dco, dcp,
-                        ctx->in[0].p, ctx->in[1].p, ctx->in[2].p, ctx->in[3].p, ctx->in[4].p, ctx->stream);
+                        static_cast<const uint32_t*>(ctx->pp_idx.p), ctx->in[5].p, ctx->in[6].p, in.cx,
+                        OutRows{ctx->in[0].p, ctx->in[1].p, ctx->in[2].p, ctx->in[3].p, ctx->in[4].p}, ctx->stream);
   if (rc) {
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
@@ -4140,40 +3894,20 @@ int cpz_prove_pairs_device(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, si
   if (rc) return rc;
   if (!rows_aligned(rows, 7)) return fail(CPZ_EINVAL, "device rows must be 16-byte aligned");
   if ((reinterpret_cast<uintptr_t>(d_pair_idx) & 3) != 0) return fail(CPZ_EINVAL, "d_pair_idx must be 4-byte aligned");
-  if (d_ctx_off && !d_ctx_bytes) return fail(CPZ_EINVAL, "ctx_off given without ctx_bytes");
+  if (int rc = check_contexts(d_ctx_bytes, d_ctx_off, n, true)) return rc;
   hipStream_t st = nullptr;
-  {
-    // The indices, on the device, as cpz_verify_each_pairs_device checks them: the lowest
-    // offending entry in one word, read back here before any kernel that follows an index into
-    // the descriptor table is enqueued, and before any output is written.
+  {  // the indices, before any output is written
     CallLock lock(ctx);
     CPZ_HIP(hipSetDevice(ctx->device));
     st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     if ((rc = order_after_last(ctx, st))) return rc;
-    CPZ_HIP(ctx->bp_word.ensure(2 * sizeof(uint32_t)));
-    uint32_t* word = static_cast<uint32_t*>(ctx->bp_word.p);
-    uint32_t first[2] = {cpz::kPairIdxOk, 0};
-    CPZ_HIP(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
-    CPZ_HIP(cpz::launch_pair_idx_check(d_pair_idx, (int64_t)n, (uint32_t)npairs, word, st));
-    CPZ_HIP(hipMemcpyAsync(&first[0], word, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CPZ_HIP(hipStreamSynchronize(st));
-    if (first[0] != cpz::kPairIdxOk) {
-      CPZ_HIP(hipMemcpyAsync(&first[1], d_pair_idx + first[0], sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      CPZ_HIP(hipStreamSynchronize(st));
-      return fail(CPZ_EINVAL, "pair_idx[" + std::to_string(first[0]) + "] = " + std::to_string(first[1]) +
-                                  " is not below npairs (" + std::to_string(npairs) + ")");
-    }
+    if ((rc = check_pair_indices_device(ctx, d_pair_idx, n, npairs, st))) return rc;
   }
-  if ((rc = pairs_bulk_generator_checks(ctx, 0, npairs, pairs))) return rc;
+  if ((rc = check_pairs_decode(ctx, 0, npairs, pairs))) return rc;
   CallLock lock(ctx);
-  std::vector<cpz::PairDesc> desc(npairs);
-  if ((rc = pairs_make_resident(ctx, npairs, pairs, desc.data()))) return rc;
-  if ((rc = order_after_last(ctx, st))) return rc;
-  CPZ_HIP(ctx->bp_desc.ensure(npairs * sizeof(cpz::PairDesc)));
-  CPZ_HIP(hipMemcpyAsync(ctx->bp_desc.p, desc.data(), npairs * sizeof(cpz::PairDesc), hipMemcpyHostToDevice, st));
-  CPZ_HIP(hipStreamSynchronize(st));  // a pageable source: read before `desc` goes
-  rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p), d_pair_idx, d_x, d_k, d_ctx_bytes,
-                        d_ctx_off, d_ctx_present, d_y1, d_y2, d_r1, d_r2, d_s, st);
+  if ((rc = pairs_resident_on_device(ctx, npairs, pairs, st))) return rc;
+  rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p), d_pair_idx, d_x, d_k,
+                        Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present), OutRows{d_y1, d_y2, d_r1, d_r2, d_s}, st);
   if (rc) {
     (void)hipStreamSynchronize(st);
     return rc;
@@ -4198,8 +3932,8 @@ int cpz_prove_synthetic_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t 
   if (rc) return rc;
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   if ((rc = order_after_last(ctx, st))) return rc;
-  rc = prove_impl(ctx, n, first_index, seed_x, seed_k, nullptr, nullptr, d_ctx_bytes, d_ctx_off, d_ctx_present, d_y1,
-                  d_y2, d_r1, d_r2, d_s, st);
+  rc = prove_impl(ctx, n, first_index, seed_x, seed_k, nullptr, nullptr, Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present),
+                  OutRows{d_y1, d_y2, d_r1, d_r2, d_s}, st);
   if (rc) return rc;
   return record_last(ctx, st);
 }
@@ -4231,7 +3965,7 @@ int cpz_verify_response_device(cpz_ctx* ctx, const uint8_t g[32], const uint8_t 
   if (rc) return rc;
   hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
   if ((rc = order_after_last(ctx, st))) return rc;
-  rc = verify_response_impl(ctx, n, d_y1, d_y2, d_r1, d_r2, d_s, d_c, static_cast<uint8_t*>(d_status_out), st);
+  rc = verify_response_impl(ctx, n, Rows(d_y1, d_y2, d_r1, d_r2, d_s), d_c, static_cast<uint8_t*>(d_status_out), st);
   if (rc) return rc;
   return record_last(ctx, st);
 }
@@ -4254,17 +3988,13 @@ int cpz_verify_response_ex(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], co
   if (rc) return rc;
   if ((rc = order_after_last(ctx, ctx->stream))) return rc;
   const uint8_t* host[5] = {y1, y2, r1, r2, s};
-  const void* dev[5];
-  const void* dcb;
-  const uint64_t* dco;
-  const uint8_t* dcp;
-  rc = stage_inputs(ctx, n, host, 5, nullptr, nullptr, nullptr, dev, &dcb, &dco, &dcp);
+  Staged in;
+  rc = stage_inputs(ctx, n, host, 5, nullptr, nullptr, nullptr, in);
   if (rc) return rc;
   CPZ_HIP(ctx->in[5].ensure(n * 32));
   CPZ_HIP(hipMemcpyAsync(ctx->in[5].p, c, n * 32, hipMemcpyHostToDevice, ctx->stream));
   CPZ_HIP(ctx->st.ensure(n));
-  rc = verify_response_impl(ctx, n, dev[0], dev[1], dev[2], dev[3], dev[4], ctx->in[5].p,
-                            static_cast<uint8_t*>(ctx->st.p), ctx->stream);
+  rc = verify_response_impl(ctx, n, in.rows, ctx->in[5].p, static_cast<uint8_t*>(ctx->st.p), ctx->stream);
   if (rc) return rc;
   CPZ_HIP(hipMemcpyAsync(status_out, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
   CPZ_HIP(hipStreamSynchronize(ctx->stream));
