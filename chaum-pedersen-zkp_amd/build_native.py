@@ -20,6 +20,9 @@
 * ``tests/native/libcpz_pairsumprobe.so`` -- the same for rlc.hip's per-pair sum kernels
                            (tests/native/pairsumprobe.hip), for the GPU unit tests only; never
                            linked into the product.
+* ``tests/native/libcpz_prepprobe.so`` -- the same for rlc.hip's prepare kernels, the extras' kernels
+                           and the device scalar arithmetic (tests/native/prepprobe.hip), for the
+                           GPU unit tests only; never linked into the product.
 * ``oracle/``            -- delegated to oracle/Makefile (the C oracle: CPU baseline and
                            at-scale checker; test infrastructure only).
 
@@ -44,6 +47,7 @@ PARTPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partprobe.so")
 PARTPAIRSPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partpairsprobe.so")
 MSMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_msmprobe.so")
 PAIRSUMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_pairsumprobe.so")
+PREPPROBE = os.path.join(ROOT, "tests", "native", "libcpz_prepprobe.so")
 ARCH = os.environ.get("CPZ_OFFLOAD_ARCH", "gfx950")
 
 
@@ -216,6 +220,22 @@ def build_pairsumprobe(force: bool = False, out: str = PAIRSUMPROBE, include: st
     return out
 
 
+def build_prepprobe(force: bool = False, out: str = PREPPROBE, include: str = CSRC) -> str:
+    """Probes of the batch check's prepare stage, the extras' kernels and the device scalar
+    arithmetic (tests/native/prepprobe.hip, which includes rlc.hip itself), compiled like the
+    product's units.  `out` / `include` build them over another copy of csrc (a mutated one) for
+    tests/test_gpu_prep_probe.py's CPZ_PREPPROBE."""
+    src = os.path.join(ROOT, "tests", "native", "prepprobe.hip")
+    deps = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h") or f == "rlc.hip"]
+    if not force and not _newer(out, [src] + deps):
+        return out
+    tmp = out + ".tmp"
+    _run([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", include,
+          "-I", os.path.join(ROOT, "include"), "-shared", src, "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 CPP_TEST = os.path.join(ROOT, "tests", "cpp", "batch_verifier_test")
 
 
@@ -281,6 +301,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_partpairsprobe(force)
     build_msmprobe(force)
     build_pairsumprobe(force)
+    build_prepprobe(force)
     build_cpp_test(force)
     build_dropin_test(force)
     build_merge_groups_test(force)

@@ -189,6 +189,12 @@ void cpzt_sc_add(uint8_t* out, const uint8_t* a, const uint8_t* b) {
   bytes_from(out, sc_add(A, B).w);
 }
 
+void cpzt_sc_neg(uint8_t* out, const uint8_t* a) {
+  sc A;
+  words_from(A.w, a);
+  bytes_from(out, sc_neg(A).w);
+}
+
 int cpzt_sc_canonical(const uint8_t* s) {
   uint32_t w[8];
   words_from(w, s);

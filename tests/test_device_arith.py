@@ -11,6 +11,7 @@ import random
 import pytest
 
 import pyoracle as O
+import scalar_vectors as SV
 from split_cases import euclid_half, half_split_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -142,6 +143,18 @@ def test_scalars(lib):
         lib.cpzt_sc_add(out, a.to_bytes(32, "little"), b.to_bytes(32, "little")); assert fi(out.raw) == (a + b) % L
     for v in [0, 1, L - 1, L, L + 1, 2**253, 2**255, 2**256 - 1]:
         assert lib.cpzt_sc_canonical(v.to_bytes(32, "little")) == (1 if v < L else 0)
+    # the edge families of tests/scalar_vectors.py: the list the gfx950 build runs as well
+    # (tests/test_gpu_prep_probe.py); rlc_weight and recode16 are device-only code
+    for x in SV.reduce_wide_cases():
+        lib.cpzt_sc_reduce_wide(out, x.to_bytes(64, "little")); assert fi(out.raw) == x % L, hex(x)
+    for a, b in SV.grid_pairs():
+        ab, bb = a.to_bytes(32, "little"), b.to_bytes(32, "little")
+        lib.cpzt_sc_mul(out, ab, bb); assert fi(out.raw) == a * b % L, (hex(a), hex(b))
+        lib.cpzt_sc_add(out, ab, bb); assert fi(out.raw) == (a + b) % L, (hex(a), hex(b))
+    for a in SV.grid_values():
+        lib.cpzt_sc_neg(out, a.to_bytes(32, "little")); assert fi(out.raw) == (-a) % L, hex(a)
+    for v in SV.CANONICAL_CASES:
+        assert lib.cpzt_sc_canonical(v.to_bytes(32, "little")) == (1 if v < L else 0), hex(v)
 
 
 def test_hashes(lib, golden):
