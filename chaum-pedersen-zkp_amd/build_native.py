@@ -23,6 +23,10 @@
 * ``tests/native/libcpz_prepprobe.so`` -- the same for rlc.hip's prepare kernels, the extras' kernels
                            and the device scalar arithmetic (tests/native/prepprobe.hip), for the
                            GPU unit tests only; never linked into the product.
+* ``tests/native/libcpz_microprobe.so`` -- gfx950 build of csrc/kernels.hip, included unchanged,
+                           behind plain C probes of the small per-pair generator tables
+                           (tests/native/microprobe.hip), for the GPU unit tests only; never linked
+                           into the product.
 * ``oracle/``            -- delegated to oracle/Makefile (the C oracle: CPU baseline and
                            at-scale checker; test infrastructure only).
 
@@ -48,6 +52,7 @@ PARTPAIRSPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partpairsprobe.so
 MSMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_msmprobe.so")
 PAIRSUMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_pairsumprobe.so")
 PREPPROBE = os.path.join(ROOT, "tests", "native", "libcpz_prepprobe.so")
+MICROPROBE = os.path.join(ROOT, "tests", "native", "libcpz_microprobe.so")
 ARCH = os.environ.get("CPZ_OFFLOAD_ARCH", "gfx950")
 
 
@@ -236,6 +241,22 @@ def build_prepprobe(force: bool = False, out: str = PREPPROBE, include: str = CS
     return out
 
 
+def build_microprobe(force: bool = False, out: str = MICROPROBE, include: str = CSRC) -> str:
+    """Probes of the small per-pair generator tables of cpz_verify_each_pairs_many
+    (tests/native/microprobe.hip, which includes kernels.hip itself), compiled like the product's
+    units.  `out` / `include` build them over another copy of csrc (a mutated one) for
+    tests/test_gpu_pair_micro_probe.py's CPZ_MICROPROBE."""
+    src = os.path.join(ROOT, "tests", "native", "microprobe.hip")
+    deps = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h") or f == "kernels.hip"]
+    if not force and not _newer(out, [src] + deps):
+        return out
+    tmp = out + ".tmp"
+    _run([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", include,
+          "-I", os.path.join(ROOT, "include"), "-shared", src, "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 CPP_TEST = os.path.join(ROOT, "tests", "cpp", "batch_verifier_test")
 
 
@@ -302,6 +323,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_msmprobe(force)
     build_pairsumprobe(force)
     build_prepprobe(force)
+    build_microprobe(force)
     build_cpp_test(force)
     build_dropin_test(force)
     build_merge_groups_test(force)

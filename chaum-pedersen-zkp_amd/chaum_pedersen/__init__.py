@@ -451,6 +451,27 @@ class Gpu:
             _ptr(off), _ptr(present), _ptr(out)))
         return out
 
+    def verify_each_pairs_many(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, contexts=None,
+                               equations_only: bool = False) -> np.ndarray:
+        """verify_each_pairs_bulk over up to EACH_PAIRS_MANY_MAX pairs (cpz_verify_each_pairs_many):
+        a tenant per entry with exact statuses, the same statuses as verify_each_pairs.  Up to
+        PAIRS_MAX pairs it is verify_each_pairs_bulk.  Above, every pair gets small tables
+        (multiples 0..8 of g, 2^128 g, h, 2^128 h: 5,760 bytes a pair) built in one launch per
+        call; no 128-entry set is built and the context's cached sets are not touched.  pairs:
+        Parameters, their type checked here; pair_idx: n integers in [0, len(pairs)), checked
+        here before the library is called."""
+        n = len(y1)
+        gh = _pair_rows(pairs)
+        npairs = len(pairs)
+        idx = _pair_indices(pair_idx, n, npairs)
+        arrs = [_rows(a, n, nm) for a, nm in ((y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2"), (s, "s"))]
+        blob, off, present = _ctx_arrays(contexts, n)
+        out = np.empty(n, dtype=np.uint8)
+        _native.check(self._lib.cpz_verify_each_pairs_many(
+            self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
+            _ptr(off), _ptr(present), _ptr(out)))
+        return out
+
     def challenges(self, y1, y2, r1, r2, contexts=None, params: Optional[Parameters] = None) -> np.ndarray:
         params = params or Parameters()
         n = len(y1)
@@ -977,9 +998,10 @@ class BatchVerifier:
         with its exact fallback (cpz_verify_batch), a smaller one cpz_verify_each.  Unlike gpu.rs,
         which issues one synchronous call per group, two or more smaller groups go out together
         as one cpz_verify_each_pairs call (one verify launch, every entry under its own pair's
-        tables; one call per 64 pairs should there be more); a single smaller group keeps
-        cpz_verify_each.  The weight indices, the rng draws and every returned status are the
-        per-group sequence's.
+        tables); more than 64 such groups go out as one cpz_verify_each_pairs_many call (every pair's
+        small tables built in that call, up to 4096 pairs and 2^20 entries a call) instead of one
+        call per 64 pairs; a single smaller group keeps cpz_verify_each.  The weight indices, the
+        rng draws and every returned status are the per-group sequence's.
 
         `rng` is drawn exactly as the reference draws it: nothing for a one-entry batch
         (verify_one, batch.rs:178-180), otherwise one 64-byte random_scalar per entry
@@ -1038,10 +1060,15 @@ class BatchVerifier:
             first_index += len(idx)
         if merge:
             # the per-proof groups in one call per PAIRS_MAX pairs (and PAIRS_MAX_PROOFS entries),
-            # entries in batch order
+            # entries in batch order; more than PAIRS_MAX groups: one verify_each_pairs_many call
+            # (per EACH_PAIRS_MANY_MAX pairs and PAIRS_BULK_MAX_PROOFS entries) instead
+            many = len(per_proof) > _native.PAIRS_MAX
+            max_pairs = _native.EACH_PAIRS_MANY_MAX if many else _native.PAIRS_MAX
+            max_proofs = _native.PAIRS_BULK_MAX_PROOFS if many else _native.PAIRS_MAX_PROOFS
+            verify_pairs = gpu.verify_each_pairs_many if many else gpu.verify_each_pairs
             calls, cur, cur_n = [], [], 0
             for gh, idx in per_proof:
-                if cur and (len(cur) == _native.PAIRS_MAX or cur_n + len(idx) > _native.PAIRS_MAX_PROOFS):
+                if cur and (len(cur) == max_pairs or cur_n + len(idx) > max_proofs):
                     calls.append(cur)
                     cur, cur_n = [], 0
                 cur.append((gh, idx))
@@ -1057,7 +1084,7 @@ class BatchVerifier:
                 which = {i: p for p, (_, idx) in enumerate(call) for i in idx}
                 order = sorted(which)
                 rows, ctxs = rows_of(order)
-                status[np.array(order)] = gpu.verify_each_pairs(
+                status[np.array(order)] = verify_pairs(
                     [Parameters(g, h) for (g, h), _ in call], np.array([which[i] for i in order], np.uint32), *rows,
                     contexts=ctxs, equations_only=True)
         return [VerifyResult(s) for s in status]

@@ -38,13 +38,14 @@ EXPORTED = (
     "cpz_verify_each_pairs", "cpz_verify_each_pairs_ex", "cpz_verify_batch_pairs", "cpz_verify_batch_pairs_ex",
     "cpz_verify_each_pairs_bulk", "cpz_verify_each_pairs_bulk_ex", "cpz_verify_each_pairs_device",
     "cpz_prove_pairs", "cpz_prove_pairs_device", "cpz_ctx_load_pairs", "cpz_ctx_pairs_resident",
-    "cpz_verify_batch_pairs_many",
+    "cpz_verify_batch_pairs_many", "cpz_verify_each_pairs_many",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
 BATCH_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_BATCH_PAIRS_MAX_PROOFS: proofs per cpz_verify_batch_pairs call
 BATCH_PAIRS_MANY_MAX = 4096        # CPZ_BATCH_PAIRS_MANY_MAX: pairs per cpz_verify_batch_pairs_many call
 PAIRS_BULK_MAX_PROOFS = 1 << 20   # CPZ_PAIRS_BULK_MAX_PROOFS: proofs per cpz_verify_each_pairs_bulk / _device call
+EACH_PAIRS_MANY_MAX = 4096        # CPZ_EACH_PAIRS_MANY_MAX: pairs per cpz_verify_each_pairs_many call
 PROVE_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_PROVE_PAIRS_MAX_PROOFS: proofs per cpz_prove_pairs / _device call
 CALL_EQUATIONS_ONLY = 1   # CPZ_CALL_EQUATIONS_ONLY: commitment checks off for one call
 CALL_PARTITIONED = 2      # CPZ_CALL_PARTITIONED: cpz_verify_batch_pairs_ex searches a failing batch by blocks
@@ -94,6 +95,9 @@ def _declare(lib):
     lib.cpz_verify_each_pairs_bulk_ex.restype = ctypes.c_int
     lib.cpz_verify_each_pairs_bulk_ex.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] +
                                                   [_p] * 5 + [_p, _p, _p, _p])
+    lib.cpz_verify_each_pairs_many.restype = ctypes.c_int
+    lib.cpz_verify_each_pairs_many.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] +
+                                               [_p] * 5 + [_p, _p, _p, _p])
     lib.cpz_verify_each_pairs_device.restype = ctypes.c_int
     lib.cpz_verify_each_pairs_device.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] +
                                                  [_p] * 5 + [_p, _p, _p, _p, _p])

@@ -118,6 +118,13 @@ struct ProbeGatherArgs {
 #endif
 constexpr int64_t kQuadVerifyMax = CPZ_QUAD_MAX;
 constexpr int kQuadTableInts = 2 * 9 * 40;  // per quad: two tables of 9 entries of 4 x 10 limbs
+// A pair's small generator tables (cpz_verify_each_pairs_many, k_pair_micro): the cached
+// multiples 0..8 of g, 2^128 g, h, 2^128 h in that order, each table in quad_table's layout
+// (9 entries of 4 fields x 10 limbs, the layout quad_lookup reads).  5,760 bytes per pair.
+constexpr int kPairMicroTableInts = 9 * 40;
+constexpr int kPairMicroTables = 4;
+constexpr int kPairMicroInts = kPairMicroTables * kPairMicroTableInts;
+constexpr int64_t kPairMicroBytes = (int64_t)kPairMicroInts * 4;
 // Per-proof calls of at most this many proofs whose (g, h) has no comb in the context's cache
 // verify against the pair's 128-entry Niels tables (VerifyArgs::vtab) instead of building the
 // 128 MiB combs (~3 ms): [s'] B by radix-256 digits inside the Straus loop, +16 additions per
@@ -193,6 +200,9 @@ struct PairArgs {
   const PairDesc* desc = nullptr;      // the call's pairs (every index below is in range: checked on the
                                        // host, or by k_pair_idx_check before any launch that reads them)
   const uint32_t* pair_idx = nullptr;  // n indices into desc
+  const int32_t* micro = nullptr;      // launch_verify_quad_pairs only: the pairs' small tables
+                                       // (kPairMicroInts ints per pair, launch_pair_micro), read
+                                       // instead of the descriptors' 128-entry tables, which may be null
 };
 
 // Mixed-pair batch check (cpz_verify_batch_pairs): what k_pair_setup leaves per pair for the host
@@ -278,7 +288,14 @@ hipError_t launch_verify_wide_pairs(const VerifyArgs& a, const ChallengeArgs& ca
 // a.block_proofs proofs each of a prepared mixed-pair batch (at most a.quad_max slots; rows, a.c,
 // a.status and pa.pair_idx are the whole batch's): a.status holds the prepare's decode-level
 // statuses, entries with a non-zero one keep it and every other ends with its per-proof status.
+// With pa.micro: every proof's [s'] B from its pair's small tables (radix-16 digits of s', two more
+// additions per window) and no descriptor's 128-entry tables read; listed blocks are not served
+// (hipErrorInvalidValue).
 hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hipStream_t st);
+// The small tables of npairs pairs in one launch (k_pair_micro), from the generator words of
+// desc[p] into micro[p * kPairMicroInts ..]: a quad per (pair, generator).  A generator that does
+// not decode leaves identity tables (launch_pair_desc's flags are what rejects such a pair).
+hipError_t launch_pair_micro(const PairDesc* desc, int npairs, int32_t* micro, hipStream_t st);
 // Device-resident indices of a mixed-pair call against npairs: *first (set to kPairIdxOk by the
 // caller, on the same stream) ends as the lowest i with idx[i] >= npairs, or stays kPairIdxOk.
 constexpr uint32_t kPairIdxOk = 0xffffffffu;

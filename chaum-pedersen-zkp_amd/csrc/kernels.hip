@@ -12,6 +12,8 @@
 //   k_build_niels        Niels tables
 //   k_pair_sets_bases /  the same tables, their 16-bit-limb rows and the transcript snapshots of k >= 1
 //   k_pair_sets_entries  pairs in one pass, each pair's into its own set's buffers
+//   k_pair_micro         a quad per (pair, generator): the cached multiples 0..8 of B and 2^128 B, the small
+//                        tables of a per-proof call over more than 64 pairs (k_verify_quad's kMicro arm)
 //   k_verify_each        1 thread / proof: challenge split v c = u (mod l) with
 //                        u, |v| < 2^127 (verify.h), 4 ristretto decodes, then per equation
 //                        [v s] B - [u] y - [v] r in E[4]  <=>  [s] B - [c] y == r
@@ -30,6 +32,7 @@
 // 3 non-canonical s, 4 identity commitment, 5 zero s.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <type_traits>
 
 #include "cpz_kernels.h"
@@ -957,6 +960,56 @@ __device__ __forceinline__ ge_p3 p3_bcast(const ge_p3& P, int from) {
   return r;
 }
 
+// ---------------------------------------------------------------------------------------
+// Small per-pair generator tables (cpz_verify_each_pairs_many): what a quad keeps for -Y and
+// -+R -- quad_table's cached multiples 0..8 -- for B and 2^128 B, B = g and B = h, 5,760 bytes
+// per pair (kPairMicroInts) against the 245 KB of a light set, so that 4096 pairs are resident
+// at once.  [s'] B is then 2 x 32 signed radix-16 digits of s' (sc_recode_radix16: digits 0..31
+// on B, 32..63 on 2^128 B, the carry out of digit 31 included), two more additions in every
+// window of the Straus loop.
+// k_pair_micro: quad (p, e) builds the two tables of generator e of pair p.  Lane 0 decodes
+// desc[p]'s generator words (a failed decode leaves the identity: k_pair_desc's flags reject the
+// pair before any proof reads it); its runtime is the 128-doubling chain of a lone quad, so a
+// wave per workgroup spreads 4096 pairs' 512 waves over every SIMD of the device at once.
+// ---------------------------------------------------------------------------------------
+constexpr int kPairMicroQuads = 16;  // quads per workgroup: one wave
+static_assert(offsetof(PairDesc, gh_words) % 16 == 0, "k_pair_micro loads a generator's words as two uint4");
+
+__global__ void __launch_bounds__(4 * kPairMicroQuads) k_pair_micro(const PairDesc* __restrict__ desc, int npairs,
+                                                                    int32_t* __restrict__ micro) {
+  const int quad = blockIdx.x * kPairMicroQuads + (threadIdx.x >> 2), q = threadIdx.x & 3;
+  const int p = quad >> 1, e = quad & 1;
+  if (p >= npairs) return;  // whole quads
+  ge_p3 B = ge_identity();
+  if (q == 0) {
+    uint32_t enc[8];
+    load_words8(enc, desc[p].gh_words, e);
+    ge_p3 P;
+    if (ristretto_decode(P, enc)) B = P;
+  }
+  B = p3_bcast(B, 0);
+  int32_t* tab = micro + (int64_t)p * kPairMicroInts + 2 * e * kPairMicroTableInts;
+  quad_table(tab, B, q);
+  B = p3_dbl_n_quad(B, 128, q);
+  quad_table(tab + kPairMicroTableInts, B, q);
+}
+
+hipError_t launch_pair_micro(const PairDesc* desc, int npairs, int32_t* micro, hipStream_t st) {
+  if (npairs <= 0) return hipSuccess;
+  if (!desc || !micro) return hipErrorInvalidValue;
+  const int quads = 2 * npairs;
+  hipLaunchKernelGGL(k_pair_micro, dim3((unsigned)((quads + kPairMicroQuads - 1) / kPairMicroQuads)),
+                     dim3(4 * kPairMicroQuads), 0, st, desc, npairs, micro);
+  return hipGetLastError();
+}
+
+// One window's generator term from a pair's small tables: acc + [dg] B + [dg2] 2^128 B, lane q of
+// the quad (tb: the table of B, the table of 2^128 B right after it; dg, dg2 in [-8, 8]).
+__device__ __forceinline__ ge_p3 pair_micro_window(const ge_p3& acc, const int32_t* tb, int dg, int dg2, int q) {
+  const fe eb = quad_lookup(tb, dg, q), eb2 = quad_lookup(tb + kPairMicroTableInts, dg2, q);
+  return ge_add_quad(ge_add_quad(acc, cached_of_field(eb), q), cached_of_field(eb2), q);
+}
+
 // kVar: no comb for this (g, h) -- [s'] B comes from the Niels multiples 1..128 of B and
 // 2^128 B (a.vtab) as 2 x 16 signed radix-256 digits of s', one pair of mixed additions every
 // second window of the Straus loop (32 additions per equation against the comb's 16).
@@ -965,14 +1018,20 @@ __device__ __forceinline__ ge_p3 p3_bcast(const ge_p3& P, int from) {
 // descriptor, the four proofs of a wave and the 32 of a block generally different ones; a.comb,
 // a.vtab and a.vtab16 are unused.  The challenges (a.c) and response statuses (a.status) are
 // k_challenge_pairs'.  kPairs is a constant: the single-pair kernels compile without this arm.
+// kMicro (k_verify_quad<false, true, true, true>, more than CPZ_PAIRS_MAX pairs in a call): the
+// generator term comes from the pair's small tables instead, pa.micro + pa.pair_idx[i] *
+// kPairMicroInts -- radix-16 digits of s', pair_micro_window in every window after the Y and R
+// additions -- and no descriptor's tab is read; listed blocks are not served (the launcher refuses
+// them).  A constant too: the other instantiations compile without it.
 struct NoPairArgs {};
-template <bool kPre, bool kVar, bool kPairs = false>
+template <bool kPre, bool kVar, bool kPairs = false, bool kMicro = false>
 __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditional_t<kPairs, PairArgs, NoPairArgs> pa) {
   static_assert(!kPairs || (kVar && !kPre), "mixed pairs: variable bases, rows decoded here");
+  static_assert(!kMicro || kPairs, "small tables: mixed pairs only");
   const int t = threadIdx.x;
   int64_t i = (int64_t)blockIdx.x * 32 + (t >> 3);
   const int e = (t >> 2) & 1, q = t & 3;
-  if (a.blocks) {  // listed blocks of block_proofs proofs (the partitioned check's per-proof passes)
+  if (!kMicro && a.blocks) {  // listed blocks of block_proofs proofs (the partitioned check's per-proof passes)
     const int64_t lb = i / a.block_proofs;
     if (lb >= a.nblocks) return;
     i = (int64_t)a.blocks[lb] * a.block_proofs + i % a.block_proofs;
@@ -981,7 +1040,7 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
   if (kPre && a.status[i] != kStOk) return;      // decode-level rejection: already final
   // listed blocks of a mixed-pair batch check (runtime.hip, pairs_part): the statuses are the
   // prepare's decode-level ones, final where non-zero; the others had a clean response status
-  if (kPairs && a.blocks && a.status[i] != kStOk) return;
+  if (kPairs && !kMicro && a.blocks && a.status[i] != kStOk) return;
 #if defined(CPZ_CLOCK_PROBE)
   // timing builds only: shader-clock stamps at the phase boundaries of block 0's first proof
   uint64_t stamp[kQuadPhases];
@@ -1013,7 +1072,9 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
     }
     sc sp = sc_mul(vs, ss);
     if (vneg) sp = sc_neg(sp);
-    if constexpr (kVar)
+    if constexpr (kMicro)
+      sc_recode_radix16(sd, sp.w);    // digits 0..31 on B, digits 32..63 on 2^128 B
+    else if constexpr (kVar)
       sc_recode_radix256(sd, sp.w);   // bytes 0..15: digits on B, bytes 16..31: on 2^128 B
     else
       sc_recode_radix65536(sd, sp.w);
@@ -1041,9 +1102,11 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
   CPZ_QUAD_STAMP(3);
   // Q = [u] Y' + [|v|] R' + [s'] B: identity (mod E[4]) iff the equation holds
   const ge_niels* vt = kVar ? a.vtab : nullptr;
-  if constexpr (kPairs) vt = pa.desc[pa.pair_idx[i]].tab;
+  if constexpr (kPairs && !kMicro) vt = pa.desc[pa.pair_idx[i]].tab;
   const ge_niels* gt = kVar ? vt + e * kNielsEntries : nullptr;          // B = g or h
   const ge_niels* gt2 = kVar ? vt + (2 + e) * kNielsEntries : nullptr;   // 2^128 B
+  const int32_t* mt = nullptr;  // kMicro: the small table of B, that of 2^128 B after it
+  if constexpr (kMicro) mt = pa.micro + (int64_t)pa.pair_idx[i] * kPairMicroInts + 2 * e * kPairMicroTableInts;
   ge_p3 acc = ge_identity();
 #pragma unroll 1
   for (int j = 0; j < 4; j++) {
@@ -1066,7 +1129,11 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
       if (j != 0 || m != 7) acc = p3_dbl_n_quad(acc, 4, q);
       acc = ge_add_quad(acc, cached_of_field(ey), q);
       acc = ge_add_quad(acc, cached_of_field(er), q);
-      if constexpr (kVar) {
+      if constexpr (kMicro) {  // digit 8 (3 - j) + m of s' (and of s' >> 128)
+        const int dg = ((int32_t)(wg << (28 - 4 * m))) >> 28;
+        const int dg2 = ((int32_t)(wg2 << (28 - 4 * m))) >> 28;
+        acc = pair_micro_window(acc, mt, dg, dg2, q);
+      } else if constexpr (kVar) {
         if ((m & 1) == 0) {  // byte 4 (3 - j) + m / 2 of s' (and of s' >> 128): weight 2^(4 t), t even
           const int dg = (int32_t)(wg << (24 - 4 * m)) >> 24;
           const int dg2 = (int32_t)(wg2 << (24 - 4 * m)) >> 24;
@@ -1138,6 +1205,12 @@ hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hip
   const int64_t slots = a.blocks ? a.nblocks * (int64_t)a.block_proofs : a.n;
   if (a.pre || !a.c || !a.status || !a.scratch || !pa.desc || !pa.pair_idx || slots > a.quad_max)
     return hipErrorInvalidValue;
+  if (pa.micro) {  // the pairs' small tables; no listed blocks
+    if (a.blocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_verify_quad<false, true, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a,
+                       pa);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((k_verify_quad<false, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a, pa);
   return hipGetLastError();
 }

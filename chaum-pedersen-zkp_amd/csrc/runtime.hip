@@ -316,6 +316,7 @@ struct cpz_ctx {
   DevBuf bp_ok, bp_list, bp_scan, bp_upart;
   DevBuf bp_word;  // cpz_verify_each_pairs_device: the index check's word (k_pair_idx_check)
   DevBuf pp_idx;   // cpz_prove_pairs: the call's pair indices (its descriptors go to bp_desc)
+  DevBuf ep_micro; // cpz_verify_each_pairs_many: the call's pairs' small tables (kPairMicroBytes each)
   // load_pairs, one block: the pass's destinations and encodings, its level bases, what comes back
   DevBuf lp;
   // partitioned batch check (part.hip): sorted lists / offsets / window sums of one chunk of
@@ -2279,7 +2280,7 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
   ctx->rl_flags.release();
   ctx->rl_parts.release();
   for (DevBuf* b : {&ctx->bp_gh, &ctx->bp_setup, &ctx->bp_pts, &ctx->bp_desc, &ctx->bp_word, &ctx->pp_idx, &ctx->bp_ok,
-                    &ctx->bp_list, &ctx->bp_scan, &ctx->bp_upart})
+                    &ctx->bp_list, &ctx->bp_scan, &ctx->bp_upart, &ctx->ep_micro})
     b->release();
 #if defined(CPZ_CLOCK_PROBE)
   for (DevBuf& b : ctx->clk) b.release();
@@ -2431,12 +2432,14 @@ void pair_desc(cpz::PairDesc& d, const GenSet& e) {
 
 // A mixed-pair range on the device: rows, contexts, indices and statuses of the whole call, the
 // descriptor table with every pair's tables resident, and the challenge buffer (32 bytes per
-// proof of the call).
+// proof of the call).  micro (cpz_verify_each_pairs_many): the pairs' small tables, read instead
+// of the descriptors' 128-entry ones, which are then null.
 struct PairRange {
   Rows rows;
   Ctxs cx;
   const uint32_t* idx = nullptr;
   const cpz::PairDesc* desc = nullptr;
+  const int32_t* micro = nullptr;
   uint32_t* c = nullptr;
   uint8_t* status = nullptr;
 };
@@ -2463,6 +2466,7 @@ int launch_quad_pairs_chunks(cpz_ctx* ctx, const PairRange& r, int64_t lo, int64
     cpz::PairArgs pa;
     pa.desc = r.desc;
     pa.pair_idx = r.idx + a;
+    pa.micro = r.micro;
     cpz::VerifyArgs va = pairs_verify_args(ca);
     va.quad_max = per;
     va.scratch = static_cast<char*>(ctx->scratch.p) + (size_t)k * slab;
@@ -2563,10 +2567,11 @@ int check_pairs_decode(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_
 // The argument checks of the bulk mixed-pair calls up to the indices, in cpz_verify_each_pairs_ex's
 // order and wording (the indices follow: on the host, or on the device for the device form).
 int pairs_bulk_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const void* pair_idx,
-                           const Rows& rows, const void* status_out, size_t max_n, const char* bound) {
+                           const Rows& rows, const void* status_out, size_t max_n, const char* bound,
+                           size_t max_pairs = CPZ_PAIRS_MAX, const char* pairs_bound = "CPZ_PAIRS_MAX") {
   if (!ctx) return fail(CPZ_EINVAL, "null context");
   if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
-  if (int rc = check_npairs(npairs)) return rc;
+  if (int rc = check_npairs(npairs, max_pairs, pairs_bound)) return rc;
   if (n > max_n) return fail_exceeds("n", n, bound, max_n);
   if (!pairs || !pair_idx || !rows.complete() || !status_out) return fail(CPZ_EINVAL, "null input pointer");
   return CPZ_OK;
@@ -3573,6 +3578,75 @@ int cpz_verify_batch_pairs_many(cpz_ctx* ctx, uint32_t flags, size_t npairs, con
                                  many ? "CPZ_BATCH_PAIRS_MANY_MAX" : "CPZ_PAIRS_MAX", npairs, pairs, n, pair_idx, y1, y2,
                                  r1, r2, s, ctx_bytes, ctx_off, ctx_present, seed, first_index, partial_out, batch_ok,
                                  status_out);
+}
+
+// CPZ_EACH_MANY_FORWARD=0 in the environment, read at every call: cpz_verify_each_pairs_many takes
+// its small-table path for npairs <= CPZ_PAIRS_MAX too instead of forwarding -- for measurement
+// (tools/each_pairs_many_ab.py) and for the equality test.
+static bool each_many_forward() {
+  const char* v = std::getenv("CPZ_EACH_MANY_FORWARD");
+  return !(v && v[0] == '0');
+}
+
+static_assert(sizeof(cpz::PairDesc) == 2 * sizeof(void*) + 2 * sizeof(cpz::StrobeSnap) + (16 + 2 + 5 * 50) * 4 &&
+                  offsetof(cpz::PairDesc, tab) == 0 && offsetof(cpz::PairDesc, gh_words) == 16 + 2 * sizeof(cpz::StrobeSnap),
+              "PairDesc keeps its layout: the small tables' base travels in PairArgs");
+
+int cpz_verify_each_pairs_many(cpz_ctx* ctx, uint32_t flags, size_t npairs, const uint8_t* pairs, size_t n,
+                               const uint32_t* pair_idx, const uint8_t* y1, const uint8_t* y2, const uint8_t* r1,
+                               const uint8_t* r2, const uint8_t* s, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                               const uint8_t* ctx_present, uint8_t* status_out) {
+  // up to CPZ_PAIRS_MAX pairs this is cpz_verify_each_pairs_bulk_ex itself: resident 128-entry
+  // tables are the faster form where they fit
+  if (npairs <= CPZ_PAIRS_MAX && each_many_forward())
+    return cpz_verify_each_pairs_bulk_ex(ctx, flags, npairs, pairs, n, pair_idx, y1, y2, r1, r2, s, ctx_bytes, ctx_off,
+                                         ctx_present, status_out);
+  int rc = pairs_bulk_head_checks(ctx, npairs, pairs, n, pair_idx, Rows(y1, y2, r1, r2, s), status_out,
+                                  CPZ_PAIRS_BULK_MAX_PROOFS, "CPZ_PAIRS_BULK_MAX_PROOFS", CPZ_EACH_PAIRS_MANY_MAX,
+                                  "CPZ_EACH_PAIRS_MANY_MAX");
+  if (rc) return rc;
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  if ((rc = check_pair_indices(pair_idx, n, npairs))) return rc;  // the kernels trust them: the table gather's bound
+  if ((rc = check_pairs(npairs, pairs))) return rc;
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  // the table-less descriptors on the device; the decode flags come back (the lowest pair named)
+  if ((rc = pairs_setup_device(ctx, npairs, pairs, st))) return rc;
+  const uint8_t* host[5] = {y1, y2, r1, r2, s};
+  Staged in;
+  const void* dex = nullptr;
+  rc = stage_inputs(ctx, n, host, 5, ctx_bytes, ctx_off, ctx_present, in, false, nullptr, nullptr, pair_idx,
+                    n * sizeof(uint32_t), &dex);
+  if (rc) return rc;
+  if (!dex) return fail(CPZ_EHIP, "internal: the pair indices were not staged");
+  CPZ_HIP(ctx->st.ensure(n));
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  CPZ_HIP(ctx->ep_micro.ensure(npairs * (size_t)cpz::kPairMicroBytes));
+  PairRange r;
+  r.rows = in.rows;
+  r.cx = in.cx;
+  r.desc = static_cast<const cpz::PairDesc*>(ctx->bp_desc.p);
+  r.idx = static_cast<const uint32_t*>(dex);
+  r.micro = static_cast<const int32_t*>(ctx->ep_micro.p);
+  r.c = static_cast<uint32_t*>(ctx->c.p);
+  r.status = static_cast<uint8_t*>(ctx->st.p);
+  {
+    // every pair's small tables in one launch, on the call's stream before the chunks' streams
+    // fork from it: one stage-13 span that counts the pairs
+    StageTimer timer(ctx, 13, st);
+    timer.count = (int)npairs;
+    CPZ_HIP(cpz::launch_pair_micro(r.desc, (int)npairs, static_cast<int32_t*>(ctx->ep_micro.p), st));
+  }
+  {
+    StageTimer span(ctx, 5, st);
+    if ((rc = launch_quad_pairs_chunks(ctx, r, 0, (int64_t)n, 1, st))) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+  }
+  return read_back_statuses(ctx, n, status_out);
 }
 
 int cpz_challenges(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const uint8_t* y1,

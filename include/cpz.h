@@ -187,6 +187,41 @@ int cpz_verify_each_pairs_device(cpz_ctx *ctx, uint32_t flags, size_t npairs, co
                                  const void *d_ctx_bytes, const uint64_t *d_ctx_off,
                                  const uint8_t *d_ctx_present, void *d_status_out, void *stream);
 
+/* cpz_verify_each_pairs_bulk_ex over up to CPZ_EACH_PAIRS_MANY_MAX (g, h) pairs: the same
+ * arguments and the same statuses -- status_out[i] is what cpz_verify_each_ex reports for entry i
+ * under pairs[pair_idx[i]], every status, with CPZ_CALL_EQUATIONS_ONLY, the context's
+ * commitment-check mode and every context shape -- for callers who need exact statuses over more
+ * pairs than a context keeps resident (a tenant per entry).  Rows of `pairs` may repeat, may be
+ * the default pair and may have no entry; n may be up to CPZ_PAIRS_BULK_MAX_PROOFS.
+ *   npairs <= CPZ_PAIRS_MAX is cpz_verify_each_pairs_bulk_ex itself (the call is forwarded):
+ * resident 128-entry tables are the faster form where they fit (measured on MI355X at 64 pairs,
+ * warm: the small tables take 1.36x the time at 16,384 entries and 1.065x at 2^20; cold they are
+ * the faster form at 16,384 entries, 0.64x, and 1.03x at 2^20; profiles/each_pairs_many_ab.json).
+ * CPZ_EACH_MANY_FORWARD=0 in the environment, read at every call, sends such calls down the path
+ * below too (for measurement).
+ *   Above that the call builds no 128-entry set and no comb: the descriptors are built on the
+ * device, and every pair gets small tables -- the cached multiples 0..8 of g, 2^128 g, h and
+ * 2^128 h, 5,760 bytes per pair, all pairs in one launch, recorded as one stage-13 span whose
+ * launch count is npairs.  The entries are then verified in chunks as the bulk call's are, eight
+ * lanes per proof, [s'] g and [s'] h from the pair's small tables by radix-16 digits (four
+ * additions per window of the Straus loop instead of three).  The call does not touch the
+ * light-set cache or its least-recently-used order (cpz_ctx_pairs_resident answers the same before
+ * and after), keeps nothing across calls (the tables are rebuilt per call) and leaves
+ * cpz_ctx_fallback_stats alone.
+ * Checked before anything is launched or written, in cpz_verify_batch_pairs_many's order and
+ * wording for the pairs and the bulk call's for the rest, cpz_last_error naming the lowest
+ * offending pair or entry: n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_EACH_PAIRS_MANY_MAX,
+ * n > CPZ_PAIRS_BULK_MAX_PROOFS, a null pointer, bad context offsets or a pair_idx[i] >= npairs ->
+ * CPZ_EINVAL; a pair that is the identity, has g == h or does not decode (found by the descriptor
+ * launch, before any table is built) -> CPZ_EGENERATOR.  status_out is not written on an error.
+ * Host buffers only; the call returns synchronised. */
+#define CPZ_EACH_PAIRS_MANY_MAX 4096
+int cpz_verify_each_pairs_many(cpz_ctx *ctx, uint32_t flags, size_t npairs, const uint8_t *pairs, size_t n,
+                               const uint32_t *pair_idx, const uint8_t *y1, const uint8_t *y2,
+                               const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
+                               const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                               const uint8_t *ctx_present, uint8_t *status_out);
+
 /* The light-set cache behind the mixed-pair calls (cpz_verify_each_pairs*, cpz_prove_pairs*, the
  * fallback of cpz_verify_batch_pairs): a context keeps the 128-entry tables and transcript
  * prefixes of its CPZ_PAIRS_MAX most recently used pairs, and a call finds which of its pairs
@@ -546,11 +581,14 @@ int cpz_verify_batch_multi(cpz_ctx *const *ctxs, int nctx, const uint8_t g[32], 
  * others when a new pair's combs do not fit); phases of the RLC MSM (inside stage 3): 8 = bucket
  * sort, 9 = bucket accumulation (k_rlc_bucket), 10 = bucket fix-up, 11 = bucket reduction
  * (segment + window), 12 = window combine + encode (k_rlc_final16); 13 = variable-base generator
- * tables (a per-proof call of at most 16384 proofs on a pair other than the default one and
+ * tables (a per-proof call of at most the eight-lane bound -- 16384 proofs on MI355X, smaller on
+ * parts with fewer CUs -- on a pair other than the default one and
  * without combs in the cache builds only the pair's Niels tables and transcript prefix, ~0.5 ms
  * instead of ~3 ms, and verifies [s'] g, [s'] h from them; a context keeps 64 such pairs; a
  * mixed-pair call or cpz_ctx_load_pairs builds all of its missing pairs' tables in one pass,
- * recorded as one span whose launch count is the number of sets built);
+ * recorded as one span whose launch count is the number of sets built; cpz_verify_each_pairs_many
+ * above CPZ_PAIRS_MAX pairs builds every pair's small tables in one launch, recorded as one span
+ * whose launch count is npairs);
  * phases of the partitioned check (inside stage 3): 14 = every block's bucket walk
  * (k_part_acc), 15 = the locate pass's walk over the failing blocks.
  * cpz_ctx_stage_times synchronises, writes the summed milliseconds and launch counts per stage

@@ -55,6 +55,7 @@ pub const CPZ_BATCH_PAIRS_MAX_PROOFS: usize = 1048576;
 pub const CPZ_BATCH_PAIRS_PART_MIN: usize = 524288;
 pub const CPZ_BATCH_PAIRS_MANY_MAX: usize = 4096;
 pub const CPZ_PAIRS_BULK_MAX_PROOFS: usize = 1048576;
+pub const CPZ_EACH_PAIRS_MANY_MAX: usize = 4096;
 pub const CPZ_PROVE_PAIRS_MAX_PROOFS: usize = 1048576;
 pub const CPZ_FALLBACK_STATS: usize = 8;
 pub const CPZ_FALLBACK_NONE: u64 = 0;
@@ -99,6 +100,10 @@ extern "C" {
                                          pair_idx: *const u32, y1: *const u8, y2: *const u8, r1: *const u8,
                                          r2: *const u8, s: *const u8, ctx_bytes: *const u8, ctx_off: *const u64,
                                          ctx_present: *const u8, status_out: *mut u8) -> c_int;
+    pub fn cpz_verify_each_pairs_many(ctx: *mut cpz_ctx, flags: u32, npairs: usize, pairs: *const u8, n: usize,
+                                      pair_idx: *const u32, y1: *const u8, y2: *const u8, r1: *const u8,
+                                      r2: *const u8, s: *const u8, ctx_bytes: *const u8, ctx_off: *const u64,
+                                      ctx_present: *const u8, status_out: *mut u8) -> c_int;
     pub fn cpz_verify_each_pairs_device(ctx: *mut cpz_ctx, flags: u32, npairs: usize, pairs: *const u8, n: usize,
                                         d_pair_idx: *const u32, d_y1: *const c_void, d_y2: *const c_void,
                                         d_r1: *const c_void, d_r2: *const c_void, d_s: *const c_void,
