@@ -44,6 +44,12 @@
 #define CPZ_ASSERT(c) ((void)0)
 #endif
 
+// CPZ_SQ2_FOLD (0 for the form before it): fe_sq2 takes 2 f, 4 f, 8 f as the multiples of its
+// first operand instead of doubling its ten 64-bit column sums.
+#ifndef CPZ_SQ2_FOLD
+#define CPZ_SQ2_FOLD 1
+#endif
+
 namespace cpz {
 
 #if defined(CPZ_COUNT_OPS) && !defined(__HIP_DEVICE_COMPILE__)
@@ -230,32 +236,41 @@ CPZ_HD fe fe_mul(const fe& f, const fe& g) {
   return r;
 }
 
-// Column sums of f^2 (using f_i f_j = f_j f_i: 55 products), each started at bias_k / div
-// (div == 0: unbiased, for fe_carry_floor).
-CPZ_HD void fe_sq_wide(int64_t h[10], const fe& f, int div) {
+// A factor 2 on a square rides on the first operand's multiples (kScale = 2: f -> 2 f, 2 f ->
+// 4 f, 4 f -> 8 f, each one 32-bit shift of a limb) instead of doubling the ten 64-bit columns
+// afterwards.  8 * |limb| < 2^29.7 for a loose operand, and the doubled worst column,
+// 2 * 267 * kLooseBound^2 < 2^62.5, still fits (these are the doubled sums fe_sq2 always carried).
+static_assert(8LL * kLooseBound < (1LL << 31), "8 f of a loose limb is a 32-bit multiplicand");
+static_assert(2.0 * 267.0 * (double)kLooseBound * (double)kLooseBound < 9.2e18, "doubled column below 2^63");
+
+// Column sums of kScale * f^2 (using f_i f_j = f_j f_i: 55 products), each started at
+// bias_k / div (div == 0: unbiased, for fe_carry_floor).
+template <int kScale>
+CPZ_HD void fe_sq_cols(int64_t h[10], const fe& f, int div) {
+  static_assert(kScale == 1 || kScale == 2, "the multiples of f are f, 2 f, 4 f, 8 f");
   CPZ_COUNT(sq);
   fe_check_operand(f);
-  int32_t f2[10], f19[10];
+  int32_t f19[10];
 #pragma unroll
-  for (int i = 0; i < 10; i++) {
-    f2[i] = (int32_t)(2u * (uint32_t)f.v[i]);
-    f19[i] = (int32_t)(19u * (uint32_t)f.v[i]);
-  }
+  for (int i = 0; i < 10; i++) f19[i] = (int32_t)(19u * (uint32_t)f.v[i]);
   bool first[10] = {true, true, true, true, true, true, true, true, true, true};
 #pragma unroll
   for (int i = 0; i < 10; i++) {
 #pragma unroll
     for (int j = i; j < 10; j++) {
       const int k = (i + j) % 10;
-      // coefficient = (i != j ? 2 : 1) * (both odd ? 2 : 1) * (i + j >= 10 ? 19 : 1)
-      const int m2 = (i != j ? 2 : 1) * (((i & 1) && (j & 1)) ? 2 : 1);
-      const int32_t a = (m2 == 1) ? f.v[i] : (m2 == 2 ? f2[i] : (int32_t)(2u * (uint32_t)f2[i]));
+      // coefficient = (i != j ? 2 : 1) * (both odd ? 2 : 1) * (i + j >= 10 ? 19 : 1), times kScale
+      const int m = kScale * (i != j ? 2 : 1) * (((i & 1) && (j & 1)) ? 2 : 1);
+      const int32_t a = (int32_t)((uint32_t)m * (uint32_t)f.v[i]);
+      CPZ_ASSERT((int64_t)a == (int64_t)m * f.v[i]);
       const int32_t b = (i + j >= 10) ? f19[j] : f.v[j];
       h[k] = acc_pin((int64_t)a * (int64_t)b + (first[k] ? (div ? carry_bias(k) / div : 0) : h[k]));
       first[k] = false;
     }
   }
 }
+
+CPZ_HD void fe_sq_wide(int64_t h[10], const fe& f, int div) { fe_sq_cols<1>(h, f, div); }
 
 // h = f^2.
 CPZ_HD fe fe_sq(const fe& f) {
@@ -265,15 +280,34 @@ CPZ_HD fe fe_sq(const fe& f) {
   return r;
 }
 
-// h = 2 f^2 (tight), as dalek's square2: the doubling is folded into the column sums
-// (which start at half the bias, so the doubled sums carry the full bias).
-CPZ_HD fe fe_sq2(const fe& f) {
+// h = 2 f^2 (tight), as dalek's square2, with the doubling done on the column sums: they start
+// at half the bias, so the doubled sums carry the full bias.  Ten 64-bit shifts (v_lshlrev_b64).
+CPZ_HD fe fe_sq2_shift(const fe& f) {
   int64_t h[10];
   fe_sq_wide(h, f, 2);
 #pragma unroll
   for (int i = 0; i < 10; i++) h[i] += h[i];
   fe r = fe_carry_biased(h);
   return r;
+}
+
+// The same columns with the factor 2 folded into the multiples of the first operand (2 f, 4 f,
+// 8 f where fe_sq_wide takes f, 2 f, 4 f) and the columns started at the full bias: every
+// column sum is exactly the doubled sum above, so the result is the same limb for limb, and no
+// 64-bit doubling is left.
+CPZ_HD fe fe_sq2_fold(const fe& f) {
+  int64_t h[10];
+  fe_sq_cols<2>(h, f, 1);
+  fe r = fe_carry_biased(h);
+  return r;
+}
+
+CPZ_HD fe fe_sq2(const fe& f) {
+#if CPZ_SQ2_FOLD
+  return fe_sq2_fold(f);
+#else
+  return fe_sq2_shift(f);
+#endif
 }
 
 // Unbiased columns -> limbs by floor carries: limb k in [0, 2^w_k) (limb 1 a few units

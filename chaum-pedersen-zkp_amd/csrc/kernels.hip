@@ -452,13 +452,55 @@ __global__ void __launch_bounds__(256) k_parse_proofs(ParseArgs a) {
 #ifndef CPZ_VERIFY_WAVES
 #define CPZ_VERIFY_WAVES 2  // waves per SIMD (256 VGPRs each)
 #endif
-// The proof's four point encodings are staged in LDS (one word column per thread): they are
+// CPZ_BUILD_LDS (0 for the form before it): the joint-table build keeps the Niels forms of Y' and
+// R' in LDS columns (scalarmul.h BuildCols, kBuildWords words per thread) instead of registers
+// that spill to scratch.  One equation's two encodings are staged at a time, in the first and the
+// last 8 of those words: r is decoded first and is dead before R's fields (the last 30 words) are
+// written, y before Y's (the first 30) are (verify.h check_equation).  With the 16 digit words a
+// block holds 76 KB of static LDS (above the 64 KB of older parts; gfx950 addresses 160 KB per
+// workgroup and the compiler accepts the plain __shared__ arrays), so two blocks still fit a
+// CU's 160 KB.
+#ifndef CPZ_BUILD_LDS
+#define CPZ_BUILD_LDS 1
+#endif
+static_assert(!CPZ_BUILD_LDS || CPZ_TABLE_LEAN, "the LDS build is the lean one");
+constexpr int kVerifyRowWords = CPZ_BUILD_LDS ? kBuildWords : 32;  // LDS words per thread beside the digits
+constexpr int kStageY = 0, kStageR = kBuildWords - 8;               // y at words 0..7, r at 52..59
+static_assert((16 + kVerifyRowWords) * kVerifyBlock * 4 <= 80 * 1024, "two k_verify_each blocks per CU");
+
+#if CPZ_BUILD_LDS
+// Stages equation e's encodings (y1, r1 or y2, r2) in the thread's column.
+struct StageRows {
+  const VerifyArgs& a;
+  int64_t i;
+  uint32_t* rows;
+  __device__ __forceinline__ void operator()(int e) const {
+    uint32_t w[8];
+    load_words8(w, e ? a.y2 : a.y1, i);
+#pragma unroll
+    for (int k = 0; k < 8; k++) rows[(kStageY + k) * kVerifyBlock] = w[k];
+    load_words8(w, e ? a.r2 : a.r1, i);
+#pragma unroll
+    for (int k = 0; k < 8; k++) rows[(kStageR + k) * kVerifyBlock] = w[k];
+  }
+};
+#endif
+
+// The proof's point encodings are staged in LDS (one word column per thread): they are
 // read once per decode, and no row address has to stay live across the Straus loops.
 __device__ __forceinline__ void verify_one_row(const VerifyArgs& a, int64_t i, const CombTable& comb_g,
                                                const CombTable& comb_h, const SlabTable& tab, uint32_t* dig,
                                                uint32_t* rows) {
-  const uint32_t* src[4] = {a.y1, a.y2, a.r1, a.r2};
   uint32_t sw[8], cw[8];
+#if CPZ_BUILD_LDS
+  load_words8(sw, a.s, i);
+  load_words8(cw, a.c, i);
+  const uint8_t st_s = a.status[i];
+  const DigitRef y{rows + kStageY * kVerifyBlock, kVerifyBlock}, r{rows + kStageR * kVerifyBlock, kVerifyBlock};
+  a.status[i] = verify_proof(y, y, r, r, sw, cw, st_s, comb_g, comb_h, tab, dig, kVerifyBlock, nullptr,
+                             a.eq_only != 0, BuildCols{rows, kVerifyBlock}, StageRows{a, i, rows});
+#else
+  const uint32_t* src[4] = {a.y1, a.y2, a.r1, a.r2};
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     uint32_t w[8];
@@ -473,6 +515,7 @@ __device__ __forceinline__ void verify_one_row(const VerifyArgs& a, int64_t i, c
       r1{rows + 16 * kVerifyBlock, kVerifyBlock}, r2{rows + 24 * kVerifyBlock, kVerifyBlock};
   a.status[i] = verify_proof(y1, y2, r1, r2, sw, cw, st_s, comb_g, comb_h, tab, dig, kVerifyBlock, nullptr,
                              a.eq_only != 0);
+#endif
 }
 
 // The RLC fallback's per-proof pass (rlc_fallback): points, challenges and decode-level
@@ -495,8 +538,15 @@ __global__ void __launch_bounds__(kVerifyBlock, CPZ_VERIFY_WAVES) k_verify_prepa
     load_words8(sw, a.s, i);
     load_words8(cw, a.c, i);
     const DigitRef none{nullptr, 0};
+#if CPZ_BUILD_LDS
+    __shared__ uint32_t bld[kBuildWords * kVerifyBlock];  // the table build's columns (scalarmul.h BuildCols)
+    a.status[i] = verify_proof<true>(none, none, none, none, sw, cw, kStOk, comb_g, comb_h, tab, dig + threadIdx.x,
+                                     kVerifyBlock, a.pre + 4 * i, a.eq_only != 0,
+                                     BuildCols{bld + threadIdx.x, kVerifyBlock});
+#else
     a.status[i] = verify_proof<true>(none, none, none, none, sw, cw, kStOk, comb_g, comb_h, tab, dig + threadIdx.x,
                                      kVerifyBlock, a.pre + 4 * i, a.eq_only != 0);
+#endif
   }
 }
 
@@ -515,7 +565,7 @@ __global__ void __launch_bounds__(kVerifyBlock, CPZ_VERIFY_WAVES) k_verify_each(
 #endif
   // digit words and point encodings in LDS, one column per thread (scalarmul.h, DigitRef)
   __shared__ uint32_t dig[16 * kVerifyBlock];
-  __shared__ uint32_t rows[32 * kVerifyBlock];
+  __shared__ uint32_t rows[kVerifyRowWords * kVerifyBlock];
 #if defined(CPZ_CLOCK_PROBE)
   // Timing variant only (tools/time_verify.py; timing_only.h): the shader clock (s_memtime) and the constant
   // 100 MHz clock (s_memrealtime) around this wave's work and the wave's hardware id, written

@@ -17,6 +17,10 @@
 //                   unmodified and X of the completed running point is negated when the sign changes
 //   CPZ_TABLE_LEAN  check_equation builds the joint table without the slot no window reads and
 //                   without squaring Z = 1
+//   CPZ_BUILD_LDS   (kernels.hip) the verify kernels build that table with the Niels forms of Y'
+//                   and R' in LDS columns (BuildCols, build_joint_table_cols below), not in
+//                   registers that spill
+//   CPZ_SQ2_FOLD    (fe25519.h) the factor 2 of fe_sq2 rides on the first operand's multiples
 #ifndef CPZ_LAZY_SIGN
 #define CPZ_LAZY_SIGN 1
 #endif
@@ -321,6 +325,98 @@ CPZ_HD void build_joint_table(const SlabTable& tab, const ge_p3& Y, const ge_p3&
       const ge_p1p1 D = p2_dbl_zz2(P.X, P.Y, fe_add(fe_one(), fe_one()));
       tab.store(neg ? joint_slot(0, 2) : joint_slot(2, 0), p3_to_cached(p1p1_to_p3(D)));
     }
+  }
+}
+
+// The lean build with its long-lived operands outside the registers (CPZ_BUILD_LDS, verify.h
+// check_equation): the affine Niels forms of Y' and R' as six field elements in word columns, word
+// w at p[w * stride] -- in the verify kernels one LDS column per thread, conflict-free as the digit
+// words are (DigitRef); the host build uses a plain array.  Field f: 0..2 = (y + x, y - x, 2 d x y)
+// of Y', 3..5 of R'.  A limb is read where a product or a sum consumes it; beside the running
+// (1, +-1) point only T of Y' stays in registers.
+constexpr int kBuildFields = 6;
+constexpr int kBuildWords = 10 * kBuildFields;
+struct BuildCols {
+  uint32_t* p;
+  int stride;
+  CPZ_HDM fe load(int f) const {
+    const uint32_t* q = p + 10 * f * stride;
+    fe r;
+#pragma unroll
+    for (int k = 0; k < 10; k++) r.v[k] = (int32_t)q[k * stride];
+    return r;
+  }
+  CPZ_HDM void store(int f, const fe& x) const {
+    uint32_t* q = p + 10 * f * stride;
+#pragma unroll
+    for (int k = 0; k < 10; k++) q[k * stride] = (uint32_t)x.v[k];
+  }
+  // x and y of the affine point whose Niels form is fields f0, f0 + 1: y + x and y - x are exact
+  // limb sums, so their half difference and half sum are the decoded limbs themselves.
+  CPZ_HDM void affine(int f0, fe& X, fe& Y) const {
+    const fe ypx = load(f0), ymx = load(f0 + 1);
+#pragma unroll
+    for (int k = 0; k < 10; k++) {
+      X.v[k] = (ypx.v[k] - ymx.v[k]) >> 1;
+      Y.v[k] = (ypx.v[k] + ymx.v[k]) >> 1;
+    }
+  }
+  // The point's Niels form into fields 3 which .. 3 which + 2 and its cached form (Z = 1) into
+  // the table: what build_joint_table writes to slots (1, 0) and (0, 1).
+  CPZ_HDM void put_point(int which, const ge_p3& P, const SlabTable& tab) const {
+    ge_cached c;
+    c.YpX = fe_add(P.Y, P.X);
+    c.YmX = fe_sub(P.Y, P.X);
+    c.Z = P.Z;
+    c.T2d = fe_mul(P.T, FE_D2());
+    store(3 * which, c.YpX);
+    store(3 * which + 1, c.YmX);
+    store(3 * which + 2, c.T2d);
+    tab.store(which ? joint_slot(0, 1) : joint_slot(1, 0), c);
+  }
+};
+
+// The remaining nine entries of build_joint_table<false> after put_point(0, Y') and
+// put_point(1, R'), with the same products in the same order on the same limbs: with the identity
+// at slot 0, which the caller stores (once for both equations of a proof: they share the slots),
+// the table is bit for bit the one build_joint_table<false> writes.  YT: T of Y'.
+//   A = Y' at the head of a pass is (x, y) from the columns, Z = 1 and YT;
+//   s R' is R' with fields 3 and 4 swapped and field 5 negated (ge_niels_cneg);
+//   2 Y', 2 R' take x, y from the columns.
+// The field index of every read depends on the loop counters, so no read is hoisted out of the
+// rolled loops into registers that would have to live across them.
+CPZ_HD void build_joint_table_cols(const SlabTable& tab, const BuildCols& cols, const fe& YT) {
+#pragma unroll 1
+  for (int neg = 0; neg < 2; neg++) {
+    const int s = neg ? -1 : 1;
+    ge_p3 A;
+    cols.affine(0, A.X, A.Y);
+    A.Z = fe_one();
+    A.T = YT;
+#pragma unroll 1
+    for (int j = 0; j < 3; j++) {
+      // j = 0: Y + s R = (1, s), kept in A;  j = 1: A + s R = (1, 2 s);  j = 2: A + Y = (2, s)
+      const int f0 = j == 2 ? 0 : 3, swap = j == 2 ? 0 : neg;
+      const fe PP = fe_mul(fe_add(A.Y, A.X), cols.load(f0 + swap));
+      const fe MM = fe_mul(fe_sub(A.Y, A.X), cols.load(f0 + 1 - swap));
+      const fe Txy2d = fe_mul(A.T, fe_cneg(cols.load(f0 + 2), -swap));
+      const fe Z2 = fe_add(A.Z, A.Z);
+      ge_p1p1 r;
+      r.X = fe_sub(PP, MM);
+      r.Y = fe_add(PP, MM);
+      r.Z = fe_add(Z2, Txy2d);
+      r.T = fe_sub(Z2, Txy2d);
+      const ge_p3 Q = p1p1_to_p3(r);
+      tab.store(j == 0 ? joint_slot(1, s) : (j == 1 ? joint_slot(1, 2 * s) : joint_slot(2, s)), p3_to_cached(Q));
+      if (j == 0) A = Q;
+    }
+    // 2 A = (2, 2) in the first pass only: (2, -2) is the slot no window reads
+    if (!neg) tab.store(joint_slot(2, 2), p3_to_cached(p1p1_to_p3(p2_dbl(ge_p2{A.X, A.Y, A.Z}))));
+    // 2 Y = (2, 0) in the first pass, 2 R = (0, 2) in the second: affine points, 2 Z^2 = 2
+    fe PX, PY;
+    cols.affine(neg ? 3 : 0, PX, PY);
+    const ge_p1p1 D = p2_dbl_zz2(PX, PY, fe_add(fe_one(), fe_one()));
+    tab.store(neg ? joint_slot(0, 2) : joint_slot(2, 0), p3_to_cached(p1p1_to_p3(D)));
   }
 }
 

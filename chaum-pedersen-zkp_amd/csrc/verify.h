@@ -272,37 +272,71 @@ CPZ_HD ge_niels niels_load(const ge_niels* p) {
 
 // kPre: the points were decoded already (pre_y / pre_r: Niels of -Y / -R from the RLC
 // prepare) and the entry's decode-level status is 0, so nothing is decoded here.
-template <bool kPre, class Comb, class Dig>
+//
+// Build: no build state outside the registers (build_joint_table, the host build), or BuildCols
+// (the verify kernels, CPZ_BUILD_LDS): each point's Niels form goes to the columns as soon as it
+// is decoded, R' first, so that only T of Y' is held, and only across the build.  The columns may
+// share their words with the encodings (kernels.hip): r is read, and tested for the identity,
+// before anything is written to R's fields, then y before Y's, and nothing reads them afterwards;
+// so r may lie anywhere in the columns and y in Y's fields.
+struct BuildInRegs {};
+template <class Build> struct build_in_cols { static constexpr bool value = false; };
+template <> struct build_in_cols<BuildCols> { static constexpr bool value = true; };
+
+template <bool kPre, class Comb, class Dig, class Build>
 CPZ_HD bool check_equation(const Dig& y, const Dig& r, const ge_niels* pre_y, const ge_niels* pre_r,
                            const Dig& udig, const Dig& vdig, bool vneg, const Dig& sdig, const Comb& comb,
-                           const SlabTable& tab, bool& decoded, bool& r_identity) {
+                           const SlabTable& tab, bool& decoded, bool& r_identity, const Build& build) {
   // One copy of the decode code for both points (a rolled loop): the kernel's instruction
   // footprint, not its arithmetic, is what the 64 KB instruction cache sees.  Then one joint
   // table of Y' = -Y and R' = -R (R when v < 0: the digits are those of |v|).
   decoded = true;
-  ge_p3 Yp, Rp;
+  r_identity = false;
+  if constexpr (build_in_cols<Build>::value) {  // (the lean build, whatever CPZ_TABLE_LEAN says)
+    // R first: T of Y' is then live from the second decode's end only, not across a decode, whose
+    // squaring chains leave no ten registers free
+    fe YT = fe_zero();
 CPZ_EQ_LOOP
-  for (int k = 0; k < 2; k++) {
-    ge_p3 P;
-    if constexpr (kPre) {
-      P = affine_from_neg_niels(niels_load(k ? pre_r : pre_y));
-    } else {
-      uint32_t w[8];
+    for (int k = 0; k < 2; k++) {
+      const bool is_r = k == 0;
+      ge_p3 P;
+      if constexpr (kPre) {
+        P = affine_from_neg_niels(niels_load(is_r ? pre_r : pre_y));
+      } else {
+        uint32_t w[8];
 #pragma unroll
-      for (int q = 0; q < 8; q++) w[q] = k ? r[q] : y[q];
-      decoded = ristretto_decode(P, w) && decoded;
+        for (int q = 0; q < 8; q++) w[q] = is_r ? r[q] : y[q];
+        if (is_r) r_identity = words8_zero(w);
+        decoded = ristretto_decode(P, w) && decoded;
+      }
+      P = (is_r && vneg) ? P : ge_neg(P);
+      build.put_point(is_r ? 1 : 0, P, tab);
+      YT = P.T;  // (the last pass's: Y')
     }
-    P = (k && vneg) ? P : ge_neg(P);
-    if (k) Rp = P; else Yp = P;
-  }
-  build_joint_table<CPZ_TABLE_LEAN == 0>(tab, Yp, Rp);  // lean: the never-read slot left unwritten
-  if constexpr (kPre) {
-    r_identity = false;
+    build_joint_table_cols(tab, build, YT);
   } else {
-    uint32_t acc = 0;
+    ge_p3 Yp, Rp;
+CPZ_EQ_LOOP
+    for (int k = 0; k < 2; k++) {
+      ge_p3 P;
+      if constexpr (kPre) {
+        P = affine_from_neg_niels(niels_load(k ? pre_r : pre_y));
+      } else {
+        uint32_t w[8];
 #pragma unroll
-    for (int q = 0; q < 8; q++) acc |= r[q];
-    r_identity = acc == 0;
+        for (int q = 0; q < 8; q++) w[q] = k ? r[q] : y[q];
+        decoded = ristretto_decode(P, w) && decoded;
+      }
+      P = (k && vneg) ? P : ge_neg(P);
+      if (k) Rp = P; else Yp = P;
+    }
+    build_joint_table<CPZ_TABLE_LEAN == 0>(tab, Yp, Rp);  // lean: the never-read slot left unwritten
+    if constexpr (!kPre) {
+      uint32_t acc = 0;
+#pragma unroll
+      for (int q = 0; q < 8; q++) acc |= r[q];
+      r_identity = acc == 0;
+    }
   }
 #if defined(CPZ_EXP_EXTRA_INV)
   // timing experiment only (timing_only.h: wrong verdicts): one field inversion per equation
@@ -324,11 +358,19 @@ CPZ_EQ_LOOP
 // which must be 0.  eq_only: an identity commitment is not reported (Commitment::new,
 // gadgets.rs:252, has no identity check; verify_one, batch.rs:185-231, checks the equations
 // only).
-template <bool kPre = false, class Comb>
+// build: where the table build keeps its state (check_equation).  stage(e) runs before equation e
+// reads its encodings: the verify kernel stages one equation's two encodings at a time there, in
+// words the build state takes over afterwards, so y1 / y2 and r1 / r2 may name the same words.
+struct StageNothing {
+  CPZ_HDM void operator()(int) const {}
+};
+
+template <bool kPre = false, class Comb, class Build = BuildInRegs, class Stage = StageNothing>
 CPZ_HD uint8_t verify_proof(const DigitRef& y1, const DigitRef& y2, const DigitRef& r1, const DigitRef& r2,
                             const uint32_t s[8], const uint32_t c[8], uint8_t st_s, const Comb& comb_g,
                             const Comb& comb_h, const SlabTable& tab_v, uint32_t* dig, int dstride,
-                            const ge_niels* pre = nullptr, bool eq_only = false) {
+                            const ge_niels* pre = nullptr, bool eq_only = false, const Build& build = Build(),
+                            const Stage& stage = Stage()) {
   bool vneg;
 #if defined(CPZ_EXP_NOSPLIT)
   // timing experiment only (wrong verdicts, timing_only.h): the challenge split, v s and the
@@ -360,11 +402,14 @@ CPZ_HD uint8_t verify_proof(const DigitRef& y1, const DigitRef& y2, const DigitR
   const DigitRef udig{dig, dstride}, vdig{dig + 4 * dstride, dstride}, sdig{dig + 8 * dstride, dstride};
   // The two equations share one copy of the code too (rolled loop over e).
   bool dec = true, id = false, eq = true;
+  // the column build leaves slot 0 to its caller: the identity, the same for both equations
+  if constexpr (build_in_cols<Build>::value) tab_v.store(0, ge_cached_identity());
 CPZ_EQ_LOOP
   for (int e = 0; e < 2; e++) {
     bool d, r_id;
+    stage(e);
     eq = check_equation<kPre>(e ? y2 : y1, e ? r2 : r1, kPre ? pre + 1 + 2 * e : nullptr, kPre ? pre + 2 * e : nullptr,
-                              udig, vdig, vneg, sdig, e ? comb_h : comb_g, tab_v, d, r_id) && eq;
+                              udig, vdig, vneg, sdig, e ? comb_h : comb_g, tab_v, d, r_id, build) && eq;
     dec = dec && d;
     id = id || r_id;
   }
