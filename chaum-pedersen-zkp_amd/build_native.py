@@ -136,7 +136,7 @@ def build_hosttest(force: bool = False, out: str = HOSTTEST, defines=()) -> str:
     the CPU tests can hold the fallback code to the same checks."""
     srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("hostlib.cpp", "hostlib_joint.cpp", "hostlib_lean.cpp",
                                                               "hostlib_prove.cpp", "hostlib_pairsum.cpp",
-                                                              "hostlib_fold.cpp")]
+                                                              "hostlib_fold.cpp", "hostlib_prove_many.cpp")]
     if not force and not _newer(out, srcs + _headers()):
         return out
     cxx = shutil.which("g++") or "g++"

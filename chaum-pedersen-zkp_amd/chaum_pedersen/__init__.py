@@ -530,6 +530,29 @@ class Gpu:
             *[_ptr(outs[q]) for q in ("y1", "y2", "r1", "r2", "s")]))
         return outs
 
+    def prove_pairs_many(self, pairs: Sequence[Parameters], pair_idx, x, k, contexts=None):
+        """prove_pairs over up to PROVE_PAIRS_MANY_MAX pairs (cpz_prove_pairs_many): a tenant per
+        entry, the same rows as prove under each entry's pair.  Up to PAIRS_MAX pairs it is
+        prove_pairs.  Above, every pair gets small tables (multiples 0..8 of g, 2^128 g, h,
+        2^128 h: 5,760 bytes a pair) built in one launch per call and every point comes from them;
+        no 128-entry set is built and the context's cached sets are not touched.  pairs:
+        Parameters, their type checked here; pair_idx: n integers in [0, len(pairs)), checked here
+        before the library is called; x, k, contexts as prove takes them.  Returns the dict of
+        (n, 32) arrays y1, y2, r1, r2, s."""
+        n = len(x)
+        gh = _pair_rows(pairs)
+        npairs = len(pairs)
+        idx = _pair_indices(pair_idx, n, npairs)
+        xs = x if isinstance(x, np.ndarray) else np.frombuffer(b"".join(_scalar_bytes(v) for v in x), np.uint8)
+        ks = k if isinstance(k, np.ndarray) else np.frombuffer(b"".join(_scalar_bytes(v) for v in k), np.uint8)
+        xs, ks = _rows(xs, n, "x"), _rows(ks, n, "k")
+        outs = {q: np.empty((n, 32), dtype=np.uint8) for q in ("y1", "y2", "r1", "r2", "s")}
+        blob, off, present = _ctx_arrays(contexts, n)
+        _native.check(self._lib.cpz_prove_pairs_many(
+            self._h, npairs, _ptr(gh), n, _ptr(idx), _ptr(xs), _ptr(ks), _ptr(blob), _ptr(off), _ptr(present),
+            *[_ptr(outs[q]) for q in ("y1", "y2", "r1", "r2", "s")]))
+        return outs
+
     def load_pairs(self, pairs: Sequence[Parameters]) -> int:
         """Make every pair's 128-entry tables resident in one pass (cpz_ctx_load_pairs), as the
         mixed-pair calls do for their own pairs: a context warmed before its first request.
@@ -760,6 +783,22 @@ class Gpu:
         dp = lambda t: None if t is None else t.data_ptr()
         _native.check(self._lib.cpz_prove_pairs_device(
             self._h, npairs, _ptr(gh), n, dp(pair_idx), dp(x), dp(k), dp(ctx_bytes), dp(ctx_off), dp(ctx_present),
+            dp(y1), dp(y2), dp(r1), dp(r2), dp(s), _torch_stream(stream)))
+
+    def prove_pairs_many_device(self, pairs: Sequence[Parameters], pair_idx, x, k, y1, y2, r1, r2, s,
+                                stream: Optional[int] = None, ctx_bytes=None, ctx_off=None, ctx_present=None) -> None:
+        """prove_pairs_many on device tensors (cpz_prove_pairs_many_device), as prove_pairs_device:
+        witnesses x, nonces k and the five output rows uint8 (n, 32), 16-B aligned; pair_idx an
+        int32 or uint32 device tensor of n elements, whose values the library checks on the device
+        before any kernel follows them (an index outside [0, len(pairs)) raises CpzError with
+        CPZ_EINVAL and leaves the outputs untouched).  Up to PROVE_PAIRS_MANY_MAX pairs.  Returns
+        with `stream` synchronised and the outputs filled."""
+        n = int(x.shape[0])
+        _pair_index_tensor(pair_idx, n)
+        gh = _pair_rows(pairs)
+        dp = lambda t: None if t is None else t.data_ptr()
+        _native.check(self._lib.cpz_prove_pairs_many_device(
+            self._h, len(pairs), _ptr(gh), n, dp(pair_idx), dp(x), dp(k), dp(ctx_bytes), dp(ctx_off), dp(ctx_present),
             dp(y1), dp(y2), dp(r1), dp(r2), dp(s), _torch_stream(stream)))
 
     def prove_synthetic_device(self, n: int, seed_x: bytes, seed_k: bytes, y1, y2, r1, r2, s, first_index: int = 0,

@@ -39,6 +39,7 @@ EXPORTED = (
     "cpz_verify_each_pairs_bulk", "cpz_verify_each_pairs_bulk_ex", "cpz_verify_each_pairs_device",
     "cpz_prove_pairs", "cpz_prove_pairs_device", "cpz_ctx_load_pairs", "cpz_ctx_pairs_resident",
     "cpz_verify_batch_pairs_many", "cpz_verify_each_pairs_many",
+    "cpz_prove_pairs_many", "cpz_prove_pairs_many_device",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
@@ -47,6 +48,7 @@ BATCH_PAIRS_MANY_MAX = 4096        # CPZ_BATCH_PAIRS_MANY_MAX: pairs per cpz_ver
 PAIRS_BULK_MAX_PROOFS = 1 << 20   # CPZ_PAIRS_BULK_MAX_PROOFS: proofs per cpz_verify_each_pairs_bulk / _device call
 EACH_PAIRS_MANY_MAX = 4096        # CPZ_EACH_PAIRS_MANY_MAX: pairs per cpz_verify_each_pairs_many call
 PROVE_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_PROVE_PAIRS_MAX_PROOFS: proofs per cpz_prove_pairs / _device call
+PROVE_PAIRS_MANY_MAX = 4096       # CPZ_PROVE_PAIRS_MANY_MAX: pairs per cpz_prove_pairs_many / _device call
 CALL_EQUATIONS_ONLY = 1   # CPZ_CALL_EQUATIONS_ONLY: commitment checks off for one call
 CALL_PARTITIONED = 2      # CPZ_CALL_PARTITIONED: cpz_verify_batch_pairs_ex searches a failing batch by blocks
 BATCH_PAIRS_PART_MIN = 1 << 19   # CPZ_BATCH_PAIRS_PART_MIN: dense ranges from this size take the partitioned check
@@ -159,6 +161,11 @@ def _declare(lib):
     lib.cpz_prove_pairs_device.restype = ctypes.c_int
     lib.cpz_prove_pairs_device.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p, _p, _p, _p, _p] +
                                            [_p] * 5 + [_p])
+    lib.cpz_prove_pairs_many.restype = ctypes.c_int
+    lib.cpz_prove_pairs_many.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p, _p, _p, _p, _p] + [_p] * 5)
+    lib.cpz_prove_pairs_many_device.restype = ctypes.c_int
+    lib.cpz_prove_pairs_many_device.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p, _p, _p, _p, _p] +
+                                                [_p] * 5 + [_p])
     lib.cpz_ctx_load_pairs.restype = ctypes.c_int
     lib.cpz_ctx_load_pairs.argtypes = [_p, ctypes.c_size_t, _p, ctypes.POINTER(ctypes.c_size_t)]
     lib.cpz_ctx_pairs_resident.restype = ctypes.c_int

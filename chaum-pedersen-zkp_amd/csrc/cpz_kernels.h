@@ -305,6 +305,10 @@ hipError_t launch_prove_points(const ProveArgs& a, hipStream_t st);
 // k_prove_points with a pair per proof (PairArgs): every proof's points from its own pair's Niels
 // tables (PairDesc::tab, all eight levels); a.comb is unused.
 hipError_t launch_prove_points_pairs(const ProveArgs& a, const PairArgs& pa, hipStream_t st);
+// The same points from the pairs' small tables (k_prove_points_micro, more than CPZ_PAIRS_MAX pairs
+// in a call): pa.micro (launch_pair_micro) and pa.pair_idx are read, pa.desc and a.comb are not.  A
+// quad per proof: radix-16 digits, 124 doublings and 64 additions per point, any n in one launch.
+hipError_t launch_prove_points_micro(const ProveArgs& a, const PairArgs& pa, hipStream_t st);
 hipError_t launch_prove_response(const ProveArgs& a, hipStream_t st);
 // Bulk decode (+ re-encode when out != null) of n encodings.
 hipError_t launch_decode_encode(int64_t n, const uint32_t* pts, uint8_t* ok, uint32_t* out, hipStream_t st);

@@ -27,6 +27,7 @@
 //   k_prove_points /     synthetic-input generator: Prover::prove_with_transcript
 //   k_prove_response     (prover/mod.rs:86-131) with ChaCha20-derived witnesses/nonces
 //   k_prove_points_pairs the same points with a (g, h) pair per proof, from the pair's Niels tables
+//   k_prove_points_micro the same points over more than 64 pairs, a quad per proof, from k_pair_micro's tables
 //
 // Status codes (uint8 per proof): 0 valid, 1 equation failed, 2 undecodable point,
 // 3 non-canonical s, 4 identity commitment, 5 zero s.
@@ -1058,6 +1059,83 @@ hipError_t launch_pair_micro(const PairDesc* desc, int npairs, int32_t* micro, h
 __device__ __forceinline__ ge_p3 pair_micro_window(const ge_p3& acc, const int32_t* tb, int dg, int dg2, int q) {
   const fe eb = quad_lookup(tb, dg, q), eb2 = quad_lookup(tb + kPairMicroTableInts, dg2, q);
   return ge_add_quad(ge_add_quad(acc, cached_of_field(eb), q), cached_of_field(eb2), q);
+}
+
+// ---------------------------------------------------------------------------------------
+// Mixed-pair prover over more than CPZ_PAIRS_MAX pairs (cpz_prove_pairs_many): proof i's four
+// points from the small tables of its own pair, pa.micro + pa.pair_idx[i] * kPairMicroInts, and no
+// descriptor's 128-entry tables (pa.desc is not read here).  A quad per proof, 64 proofs per block.
+// Digits: sc_recode_radix16 of the scalar (x, then k), one recoding of all 64 digits, so that the
+// carry out of digit 31 is already in digit 32: digits 0..31 go on B, digits 32..63 on 2^128 B, and
+// sum d_i 16^i = v.  prove_scalar returns v < l < 2^252 + 2^125: nibble 63 of v is at most 1, and
+// with the carry out of digit 62 (0 or 1) at most 2 < 8, so digit 63 is 0..2 and nothing is carried
+// out of it.
+// Walk w = 2 * scalar + generator (y1, y2, r1, r2 in that order): 32 windows from the top, four
+// doublings (none before the first) and pair_micro_window -- k_verify_quad's kMicro table
+// addressing and lookups: 124 doublings and 64 additions a point.  The digit words are rotated, not
+// shifted, through the windows, so the two walks of a scalar read one recoding.  The quad arithmetic
+// leaves the sum on all four lanes; lane w keeps it, and after the fourth walk every lane encodes
+// its own point and stores its own row: the serial encoding (an inversion's square chain) runs once
+// on four lanes instead of four times on one.  One copy of the walk and one of the encoding.
+// Two waves per SIMD: without the bound the allocator takes 256 VGPRs and one AGPR, a single wave;
+// with it 256 VGPRs and no scratch (three waves would spill 268 bytes a lane).
+// ---------------------------------------------------------------------------------------
+constexpr int kProveMicroProofs = 64;  // proofs per workgroup: four waves of 16 quads
+
+__global__ void __launch_bounds__(4 * kProveMicroProofs, 2) k_prove_points_micro(ProveArgs a, PairArgs pa) {
+  const int q = threadIdx.x & 3;
+  const int64_t i = (int64_t)blockIdx.x * kProveMicroProofs + (threadIdx.x >> 2);
+  if (i >= a.n) return;  // whole quads
+  const uint64_t idx = a.first_index + (uint64_t)i;
+  const int32_t* micro = pa.micro + (int64_t)pa.pair_idx[i] * kPairMicroInts;
+  ge_p3 mine = ge_identity();
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {  // pass 0: x -> y1, y2; pass 1: k -> r1, r2
+    uint32_t sd[8];
+    {
+      const sc v = prove_scalar(pass ? a.k_in : a.x_in, pass ? a.seed_k : a.seed_x, idx, i);
+      sc_recode_radix16(sd, v.w);
+    }
+#pragma unroll 1
+    for (int e = 0; e < 2; e++) {  // B = g, then h: the table of B, that of 2^128 B after it
+      const int32_t* mt = micro + 2 * e * kPairMicroTableInts;
+      ge_p3 acc = ge_identity();
+#pragma unroll 1
+      for (int j = 0; j < 4; j++) {
+        const uint32_t wg = sd[3], wg2 = sd[7];  // digits 8 (3 - j) .. + 7 of v (and of v >> 128)
+#pragma unroll
+        for (int k = 3; k > 0; k--) {
+          sd[k] = sd[k - 1];
+          sd[4 + k] = sd[4 + k - 1];
+        }
+        sd[0] = wg;  // a full turn after four windows' words: the next walk starts from the top again
+        sd[4] = wg2;
+#pragma unroll 1
+        for (int m = 7; m >= 0; m--) {
+          const int dg = ((int32_t)(wg << (28 - 4 * m))) >> 28;
+          const int dg2 = ((int32_t)(wg2 << (28 - 4 * m))) >> 28;
+          if (j != 0 || m != 7) acc = p3_dbl_n_quad(acc, 4, q);
+          acc = pair_micro_window(acc, mt, dg, dg2, q);
+        }
+      }
+      const bool keep = q == 2 * pass + e;
+      mine.X = fe_select(mine.X, acc.X, keep);
+      mine.Y = fe_select(mine.Y, acc.Y, keep);
+      mine.Z = fe_select(mine.Z, acc.Z, keep);
+      mine.T = fe_select(mine.T, acc.T, keep);
+    }
+  }
+  uint32_t w[8];
+  ristretto_encode(w, mine);
+  store_words8(q == 0 ? a.y1 : (q == 1 ? a.y2 : (q == 2 ? a.r1 : a.r2)), i, w);
+}
+
+hipError_t launch_prove_points_micro(const ProveArgs& a, const PairArgs& pa, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (!pa.micro || !pa.pair_idx) return hipErrorInvalidValue;
+  const int64_t blocks = (a.n + kProveMicroProofs - 1) / kProveMicroProofs;
+  hipLaunchKernelGGL(k_prove_points_micro, dim3((unsigned)blocks), dim3(4 * kProveMicroProofs), 0, st, a, pa);
+  return hipGetLastError();
 }
 
 // kVar: no comb for this (g, h) -- [s'] B comes from the Niels multiples 1..128 of B and

@@ -142,6 +142,15 @@ int check_contexts(const void* ctx_bytes, const uint64_t* ctx_off, size_t n, boo
   return CPZ_OK;
 }
 
+// Host offsets rise from entry to entry (stage_inputs' check, and ahead of any launch where a call
+// enqueues work before it stages its contexts).
+int check_context_order(const uint64_t* ctx_off, size_t n) {
+  if (ctx_off)
+    for (size_t i = 0; i < n; i++)
+      if (ctx_off[i + 1] < ctx_off[i]) return fail(CPZ_EINVAL, "ctx_off must be non-decreasing");
+  return CPZ_OK;
+}
+
 // The five proof rows of a batch on the device (8 words per proof each; a call without a row
 // leaves it null) and its transcript contexts, as the kernels' argument structs take them.
 struct Rows {
@@ -872,9 +881,7 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
   const void* dev[5] = {};
   out = Staged{};
   if (status_dev) *status_dev = nullptr;
-  if (ctx_off)
-    for (size_t i = 0; i < n; i++)
-      if (ctx_off[i + 1] < ctx_off[i]) return fail(CPZ_EINVAL, "ctx_off must be non-decreasing");
+  if (int rc = check_context_order(ctx_off, n)) return rc;
   const size_t nbytes = ctx_off ? (size_t)(ctx_off[n] - ctx_off[0]) : 0;
   const size_t rows = (size_t)count * n * 32;
   const size_t o_off = rows, o_pres = pad16(o_off + (ctx_off ? (n + 1) * 8 : 0));
@@ -3844,10 +3851,11 @@ int verify_response_impl(cpz_ctx* ctx, size_t n, const Rows& rows, const void* c
 // The argument checks of both forms up to the indices, in cpz_verify_each_pairs_ex's order (the
 // indices follow: on the host, or on the device for the device form).
 int prove_pairs_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const void* pair_idx,
-                            const void* const rows[7]) {
+                            const void* const rows[7], size_t max_pairs = CPZ_PAIRS_MAX,
+                            const char* pairs_bound = "CPZ_PAIRS_MAX") {
   if (!ctx) return fail(CPZ_EINVAL, "null context");
   if (n == 0) return fail(CPZ_EEMPTY, "empty input");
-  if (int rc = check_npairs(npairs)) return rc;
+  if (int rc = check_npairs(npairs, max_pairs, pairs_bound)) return rc;
   if (n > CPZ_PROVE_PAIRS_MAX_PROOFS) return fail_exceeds("n", n, "CPZ_PROVE_PAIRS_MAX_PROOFS", CPZ_PROVE_PAIRS_MAX_PROOFS);
   if (!pairs || !pair_idx) return fail(CPZ_EINVAL, "null input pointer");
   for (int q = 0; q < 7; q++)
@@ -3859,14 +3867,28 @@ int prove_pairs_head_checks(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, s
 // pair's tables resident).  The points come from the pairs' Niels tables (k_prove_points_pairs:
 // no comb, no table slab, so one launch for any n), the challenges from k_challenge_pairs with
 // each pair's transcript prefix, the responses from k_prove_response.
+// With micro_pairs != 0 (cpz_prove_pairs_many above CPZ_PAIRS_MAX pairs): d_desc holds that many
+// table-less descriptors (pairs_setup_device), every pair's small tables are built first into
+// ctx->ep_micro -- one launch, one stage-13 span that counts the pairs -- and the points come from
+// them (k_prove_points_micro); no descriptor's tables are read and no cached set is touched.
 int prove_pairs_impl(cpz_ctx* ctx, size_t n, const cpz::PairDesc* d_desc, const uint32_t* d_idx, const void* d_x,
-                     const void* d_k, const Ctxs& cx, const OutRows& out, hipStream_t st) {
+                     const void* d_k, const Ctxs& cx, const OutRows& out, hipStream_t st, size_t micro_pairs = 0) {
   CPZ_HIP(ctx->c.ensure(n * 32));
+  if (micro_pairs) CPZ_HIP(ctx->ep_micro.ensure(micro_pairs * (size_t)cpz::kPairMicroBytes));
   const cpz::ProveArgs pa = prove_args(ctx, n, d_x, d_k, out);  // (no comb: the pairs' Niels tables)
   cpz::PairArgs pr;
   pr.desc = d_desc;
   pr.pair_idx = d_idx;
-  {
+  if (micro_pairs) {
+    pr.micro = static_cast<const int32_t*>(ctx->ep_micro.p);
+    {  // the stage-13 span closes with this block, before the stage-6 span of the point kernel opens
+      StageTimer timer(ctx, 13, st);
+      timer.count = (int)micro_pairs;
+      CPZ_HIP(cpz::launch_pair_micro(d_desc, (int)micro_pairs, static_cast<int32_t*>(ctx->ep_micro.p), st));
+    }
+    StageTimer t(ctx, 6, st);  // closes at the end of this arm: the point kernel alone
+    CPZ_HIP(cpz::launch_prove_points_micro(pa, pr, st));
+  } else {
     StageTimer t(ctx, 6, st);
     CPZ_HIP(cpz::launch_prove_points_pairs(pa, pr, st));
   }
@@ -3982,6 +4004,90 @@ int cpz_prove_pairs_device(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, si
   if ((rc = pairs_resident_on_device(ctx, npairs, pairs, st))) return rc;
   rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p), d_pair_idx, d_x, d_k,
                         Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present), OutRows{d_y1, d_y2, d_r1, d_r2, d_s}, st);
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  if ((rc = record_last(ctx, st))) return rc;
+  CPZ_HIP(hipStreamSynchronize(st));
+  return CPZ_OK;
+}
+
+// CPZ_PROVE_MANY_FORWARD=0 in the environment, read at every call: cpz_prove_pairs_many[_device]
+// takes its small-table path for npairs <= CPZ_PAIRS_MAX too instead of forwarding -- for
+// measurement (tools/prove_pairs_many_ab.py) and for the equality test.
+static bool prove_many_forward() {
+  const char* v = std::getenv("CPZ_PROVE_MANY_FORWARD");
+  return !(v && v[0] == '0');
+}
+
+int cpz_prove_pairs_many(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n, const uint32_t* pair_idx,
+                         const uint8_t* x, const uint8_t* k, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                         const uint8_t* ctx_present, uint8_t* y1, uint8_t* y2, uint8_t* r1, uint8_t* r2, uint8_t* s) {
+  // up to CPZ_PAIRS_MAX pairs this is cpz_prove_pairs itself: resident 128-entry tables take 24
+  // doublings and at most 32 additions per point, the small tables 124 and 64
+  if (npairs <= CPZ_PAIRS_MAX && prove_many_forward())
+    return cpz_prove_pairs(ctx, npairs, pairs, n, pair_idx, x, k, ctx_bytes, ctx_off, ctx_present, y1, y2, r1, r2, s);
+  const void* rows[7] = {x, k, y1, y2, r1, r2, s};
+  int rc = prove_pairs_head_checks(ctx, npairs, pairs, n, pair_idx, rows, CPZ_PROVE_PAIRS_MANY_MAX,
+                                   "CPZ_PROVE_PAIRS_MANY_MAX");
+  if (rc) return rc;
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  if ((rc = check_context_order(ctx_off, n))) return rc;  // here: the descriptor launch precedes the staging
+  if ((rc = check_pair_indices(pair_idx, n, npairs))) return rc;  // the kernels trust them: the table gather's bound
+  if ((rc = check_pairs(npairs, pairs))) return rc;
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  // the table-less descriptors on the device; the decode flags come back (the lowest pair named)
+  if ((rc = pairs_setup_device(ctx, npairs, pairs, st))) return rc;
+  Staged in;  // the contexts alone
+  const uint8_t* none[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  rc = stage_inputs(ctx, n, none, 0, ctx_bytes, ctx_off, ctx_present, in);
+  if (rc) return rc;
+  for (int q = 0; q < 7; q++) CPZ_HIP(ctx->in[q].ensure(n * 32));
+  CPZ_HIP(ctx->pp_idx.ensure(n * sizeof(uint32_t)));
+  CPZ_HIP(hipMemcpyAsync(ctx->pp_idx.p, pair_idx, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  CPZ_HIP(hipMemcpyAsync(ctx->in[5].p, x, n * 32, hipMemcpyHostToDevice, st));
+  CPZ_HIP(hipMemcpyAsync(ctx->in[6].p, k, n * 32, hipMemcpyHostToDevice, st));
+  rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p),
+                        static_cast<const uint32_t*>(ctx->pp_idx.p), ctx->in[5].p, ctx->in[6].p, in.cx,
+                        OutRows{ctx->in[0].p, ctx->in[1].p, ctx->in[2].p, ctx->in[3].p, ctx->in[4].p}, st, npairs);
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  uint8_t* outs[5] = {y1, y2, r1, r2, s};
+  for (int q = 0; q < 5; q++) CPZ_HIP(hipMemcpyAsync(outs[q], ctx->in[q].p, n * 32, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  return CPZ_OK;
+}
+
+int cpz_prove_pairs_many_device(cpz_ctx* ctx, size_t npairs, const uint8_t* pairs, size_t n,
+                                const uint32_t* d_pair_idx, const void* d_x, const void* d_k, const void* d_ctx_bytes,
+                                const uint64_t* d_ctx_off, const uint8_t* d_ctx_present, void* d_y1, void* d_y2,
+                                void* d_r1, void* d_r2, void* d_s, void* stream) {
+  if (npairs <= CPZ_PAIRS_MAX && prove_many_forward())
+    return cpz_prove_pairs_device(ctx, npairs, pairs, n, d_pair_idx, d_x, d_k, d_ctx_bytes, d_ctx_off, d_ctx_present,
+                                  d_y1, d_y2, d_r1, d_r2, d_s, stream);
+  const void* rows[7] = {d_x, d_k, d_y1, d_y2, d_r1, d_r2, d_s};
+  int rc = prove_pairs_head_checks(ctx, npairs, pairs, n, d_pair_idx, rows, CPZ_PROVE_PAIRS_MANY_MAX,
+                                   "CPZ_PROVE_PAIRS_MANY_MAX");
+  if (rc) return rc;
+  if (!rows_aligned(rows, 7)) return fail(CPZ_EINVAL, "device rows must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_pair_idx) & 3) != 0) return fail(CPZ_EINVAL, "d_pair_idx must be 4-byte aligned");
+  if ((rc = check_contexts(d_ctx_bytes, d_ctx_off, n, true))) return rc;
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  // the indices, before any output is written and before any kernel follows one into the tables
+  if ((rc = check_pair_indices_device(ctx, d_pair_idx, n, npairs, st))) return rc;
+  if ((rc = check_pairs(npairs, pairs))) return rc;
+  if ((rc = pairs_setup_device(ctx, npairs, pairs, st))) return rc;
+  rc = prove_pairs_impl(ctx, n, static_cast<const cpz::PairDesc*>(ctx->bp_desc.p), d_pair_idx, d_x, d_k,
+                        Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_present), OutRows{d_y1, d_y2, d_r1, d_r2, d_s}, st, npairs);
   if (rc) {
     (void)hipStreamSynchronize(st);
     return rc;

@@ -321,6 +321,61 @@ int cpz_prove_pairs_device(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, si
                            const uint8_t *d_ctx_present, void *d_y1, void *d_y2, void *d_r1,
                            void *d_r2, void *d_s, void *stream);
 
+/* cpz_prove_pairs / cpz_prove_pairs_device over up to CPZ_PROVE_PAIRS_MANY_MAX (g, h) pairs: the
+ * same arguments and the same outputs -- row i of every output is byte for byte what cpz_prove
+ * writes for (x_i, k_i, context i) under pairs[pair_idx[i]], scalars taken mod l, every context
+ * shape -- for callers who prove under more pairs than a context keeps resident (a tenant per
+ * entry).  Rows of `pairs` may repeat, may be the default pair and may have no entry; n may be up
+ * to CPZ_PROVE_PAIRS_MAX_PROOFS.
+ *   npairs <= CPZ_PAIRS_MAX is cpz_prove_pairs[_device] itself (the call is forwarded): resident
+ * 128-entry tables take 24 doublings and at most 32 additions per point, the small tables about
+ * 124 doublings and 64 additions.  CPZ_PROVE_MANY_FORWARD=0 in the environment, read at every
+ * call, sends such calls down the path below too (for measurement).
+ *   Above that the call builds no 128-entry set and no comb: the descriptors are built on the
+ * device, and every pair gets small tables -- the cached multiples 0..8 of g, 2^128 g, h and
+ * 2^128 h, 5,760 bytes per pair, all pairs in one launch, recorded as one stage-13 span whose
+ * launch count is npairs.  Every proof's four points then come from its own pair's small tables,
+ * four lanes per proof, by 2 x 32 signed radix-16 digits of the scalar (k_prove_points_micro), in
+ * one launch for any n; challenges and responses as in cpz_prove_pairs.  Kernel time is reported
+ * under stage 6.  The call does not touch the light-set cache or its least-recently-used order
+ * (cpz_ctx_pairs_resident answers the same before and after), keeps nothing across calls (the
+ * tables are rebuilt per call) and leaves cpz_ctx_fallback_stats alone.
+ *   Measured on MI355X against the route it replaces -- cpz_prove_pairs in runs of at most
+ * CPZ_PAIRS_MAX pairs on gathered rows -- medians (min - max) in ms, profiles/prove_pairs_many_ab.json
+ * (tools/prove_pairs_many_ab.py): 1000 entries over 1000 pairs, 1.44 (1.44 - 1.44) against 31.7
+ * (31.7 - 31.8) warm and 1.71 (1.66 - 1.78) against 32.3 (32.1 - 32.5) cold, 16 calls on the other
+ * side.  2^17 and 2^20 entries over 4096 pairs, uniform or skewed, are not measured yet (the tool
+ * runs them; the file holds no figure for them).  Where the new path is NOT the faster one: at 64
+ * pairs, hence the forwarding -- CPZ_PROVE_MANY_FORWARD=0 against the forwarded call takes 1.60
+ * (1.58 - 1.62) against 1.11 (1.10 - 1.14) ms at 16,384 entries and 59.9 (59.6 - 60.0) against 25.2
+ * (25.1 - 26.3) ms at 2^20 warm, and 60.1 against 26.8 ms at 2^20 cold; only cold at 16,384 entries
+ * are the small tables ahead, 1.98 (1.95 - 2.05) against 2.81 (2.76 - 3.16) ms.  The doubling and
+ * addition counts above are derived from the code, not measured.
+ * Both forms return synchronised.  The device form is cpz_prove_pairs_device's: 16-byte aligned
+ * device rows, n device-resident indices (`pairs` stays a host array), `stream` a hipStream_t or
+ * NULL for the context's own; it scans the indices on the device first and synchronises `stream`
+ * to read the result -- an offending index is CPZ_EINVAL naming the lowest such entry, with every
+ * output untouched -- and any later call on the same context, on any stream, is ordered after this
+ * call's kernels.
+ * Checked before anything is launched (the device form: before anything but the index scan) or
+ * written, in cpz_prove_pairs' order and wording up to the indices and
+ * cpz_verify_each_pairs_many's for the pairs, cpz_last_error naming the lowest offending pair or
+ * entry: n == 0 -> CPZ_EEMPTY; npairs == 0, npairs > CPZ_PROVE_PAIRS_MANY_MAX,
+ * n > CPZ_PROVE_PAIRS_MAX_PROOFS, a null pointer, a misaligned device row, bad context offsets or
+ * a pair_idx[i] >= npairs -> CPZ_EINVAL; a pair that is the identity, has g == h or does not
+ * decode (found by the descriptor launch, before any table is built) -> CPZ_EGENERATOR.  No
+ * output is written on an error. */
+#define CPZ_PROVE_PAIRS_MANY_MAX 4096
+int cpz_prove_pairs_many(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
+                         const uint32_t *pair_idx, const uint8_t *x, const uint8_t *k,
+                         const uint8_t *ctx_bytes, const uint64_t *ctx_off, const uint8_t *ctx_present,
+                         uint8_t *y1, uint8_t *y2, uint8_t *r1, uint8_t *r2, uint8_t *s);
+int cpz_prove_pairs_many_device(cpz_ctx *ctx, size_t npairs, const uint8_t *pairs, size_t n,
+                                const uint32_t *d_pair_idx, const void *d_x, const void *d_k,
+                                const void *d_ctx_bytes, const uint64_t *d_ctx_off,
+                                const uint8_t *d_ctx_present, void *d_y1, void *d_y2, void *d_r1,
+                                void *d_r2, void *d_s, void *stream);
+
 /* Synthetic input generator (Prover::prove_with_transcript, prover/mod.rs:86-131):
  * witness x_i and nonce k_i = from_bytes_mod_order_wide(ChaCha20(seed_x / seed_k, block
  * first_index + i)); writes y1 = x g, y2 = x h, r1 = k g, r2 = k h, s = k + c x. */
@@ -575,7 +630,8 @@ int cpz_verify_batch_multi(cpz_ctx *const *ctxs, int nctx, const uint8_t g[32], 
  * Stages: 0 = k_challenge, 1 = k_verify_each, 2 = RLC decode/weights, 3 = RLC MSM,
  * 4 = fallback, 5 = the whole per-proof verify of one call (first to last k_verify_each,
  * whose launches overlap on several streams), 6 = prover (commitments / statements, then
- * challenges + responses), 7 = generator tables (a (g, h) pair's combs and transcript prefix
+ * challenges + responses; cpz_prove_pairs_many's point kernel and its challenges + responses
+ * too), 7 = generator tables (a (g, h) pair's combs and transcript prefix
  * built: a cache miss, one launch each; a context keeps the tables of its 4 most recently used
  * pairs, or of CPZ_GEN_CACHE = 1..4 set in the environment when it is created, and frees the
  * others when a new pair's combs do not fit); phases of the RLC MSM (inside stage 3): 8 = bucket
@@ -587,8 +643,8 @@ int cpz_verify_batch_multi(cpz_ctx *const *ctxs, int nctx, const uint8_t g[32], 
  * instead of ~3 ms, and verifies [s'] g, [s'] h from them; a context keeps 64 such pairs; a
  * mixed-pair call or cpz_ctx_load_pairs builds all of its missing pairs' tables in one pass,
  * recorded as one span whose launch count is the number of sets built; cpz_verify_each_pairs_many
- * above CPZ_PAIRS_MAX pairs builds every pair's small tables in one launch, recorded as one span
- * whose launch count is npairs);
+ * and cpz_prove_pairs_many above CPZ_PAIRS_MAX pairs build every pair's small tables in one launch,
+ * recorded as one span whose launch count is npairs);
  * phases of the partitioned check (inside stage 3): 14 = every block's bucket walk
  * (k_part_acc), 15 = the locate pass's walk over the failing blocks.
  * cpz_ctx_stage_times synchronises, writes the summed milliseconds and launch counts per stage

@@ -57,6 +57,7 @@ pub const CPZ_BATCH_PAIRS_MANY_MAX: usize = 4096;
 pub const CPZ_PAIRS_BULK_MAX_PROOFS: usize = 1048576;
 pub const CPZ_EACH_PAIRS_MANY_MAX: usize = 4096;
 pub const CPZ_PROVE_PAIRS_MAX_PROOFS: usize = 1048576;
+pub const CPZ_PROVE_PAIRS_MANY_MAX: usize = 4096;
 pub const CPZ_FALLBACK_STATS: usize = 8;
 pub const CPZ_FALLBACK_NONE: u64 = 0;
 pub const CPZ_FALLBACK_BISECTION: u64 = 1;
@@ -157,6 +158,16 @@ extern "C" {
                                   d_ctx_bytes: *const c_void, d_ctx_off: *const u64, d_ctx_present: *const u8,
                                   d_y1: *mut c_void, d_y2: *mut c_void, d_r1: *mut c_void, d_r2: *mut c_void,
                                   d_s: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn cpz_prove_pairs_many(ctx: *mut cpz_ctx, npairs: usize, pairs: *const u8, n: usize, pair_idx: *const u32,
+                                x: *const u8, k: *const u8, ctx_bytes: *const u8, ctx_off: *const u64,
+                                ctx_present: *const u8, y1: *mut u8, y2: *mut u8, r1: *mut u8, r2: *mut u8,
+                                s: *mut u8) -> c_int;
+    pub fn cpz_prove_pairs_many_device(ctx: *mut cpz_ctx, npairs: usize, pairs: *const u8, n: usize,
+                                       d_pair_idx: *const u32, d_x: *const c_void, d_k: *const c_void,
+                                       d_ctx_bytes: *const c_void, d_ctx_off: *const u64,
+                                       d_ctx_present: *const u8, d_y1: *mut c_void, d_y2: *mut c_void,
+                                       d_r1: *mut c_void, d_r2: *mut c_void, d_s: *mut c_void,
+                                       stream: *mut c_void) -> c_int;
     pub fn cpz_ctx_load_pairs(ctx: *mut cpz_ctx, npairs: usize, pairs: *const u8, built_out: *mut usize) -> c_int;
     pub fn cpz_ctx_pairs_resident(ctx: *mut cpz_ctx, npairs: usize, pairs: *const u8, resident_out: *mut u8) -> c_int;
     pub fn cpz_prove_synthetic(ctx: *mut cpz_ctx, g: *const u8, h: *const u8, n: usize, first_index: u64,
