@@ -13,6 +13,9 @@
 * ``tests/native/libcpz_partpairsprobe.so`` -- the same for part.hip's pair mode
                            (tests/native/partpairsprobe.hip), for the GPU unit tests only; never
                            linked into the product.
+* ``tests/native/libcpz_partmanyprobe.so`` -- the same for part.hip's many mode (block-local pair
+                           slots, tests/native/partmanyprobe.hip), for the GPU unit tests only;
+                           never linked into the product.
 * ``tests/native/libcpz_msmprobe.so`` -- gfx950 build of csrc/rlc.hip, included unchanged, behind
                            plain C probes of the MSM's sort and reduction kernels
                            (tests/native/msmprobe.hip), for the GPU unit tests only; never linked
@@ -49,6 +52,7 @@ HOSTTEST = os.path.join(ROOT, "tests", "native", "libcpz_hosttest.so")
 DEVPROBE = os.path.join(ROOT, "tests", "native", "libcpz_devprobe.so")
 PARTPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partprobe.so")
 PARTPAIRSPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partpairsprobe.so")
+PARTMANYPROBE = os.path.join(ROOT, "tests", "native", "libcpz_partmanyprobe.so")
 MSMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_msmprobe.so")
 PAIRSUMPROBE = os.path.join(ROOT, "tests", "native", "libcpz_pairsumprobe.so")
 PREPPROBE = os.path.join(ROOT, "tests", "native", "libcpz_prepprobe.so")
@@ -195,6 +199,22 @@ def build_partpairsprobe(force: bool = False, out: str = PARTPAIRSPROBE, include
     return out
 
 
+def build_partmanyprobe(force: bool = False, out: str = PARTMANYPROBE, include: str = CSRC) -> str:
+    """Probes of the partitioned check's many-mode kernels (tests/native/partmanyprobe.hip, which
+    includes part.hip itself), compiled like the product's units.  `out` / `include` build them
+    over another copy of csrc (a mutated one) for tests/test_gpu_part_many_probe.py's
+    CPZ_PARTMANYPROBE."""
+    src = os.path.join(ROOT, "tests", "native", "partmanyprobe.hip")
+    deps = [os.path.join(include, f) for f in os.listdir(include) if f.endswith(".h") or f == "part.hip"]
+    if not force and not _newer(out, [src] + deps):
+        return out
+    tmp = out + ".tmp"
+    _run([_hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I", include,
+          "-I", os.path.join(ROOT, "include"), "-shared", src, "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 def build_msmprobe(force: bool = False, out: str = MSMPROBE, include: str = CSRC) -> str:
     """Probes of the MSM's sort and reduction kernels (tests/native/msmprobe.hip, which includes
     rlc.hip itself), compiled like the product's units.  `out` / `include` build them over
@@ -321,6 +341,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_devprobe(force)
     build_partprobe(force)
     build_partpairsprobe(force)
+    build_partmanyprobe(force)
     build_msmprobe(force)
     build_pairsumprobe(force)
     build_prepprobe(force)

@@ -634,14 +634,21 @@ class Gpu:
 
     def verify_batch_pairs_many(self, pairs: Sequence[Parameters], pair_idx, y1, y2, r1, r2, s, seed: bytes,
                                 first_index: int = 0, contexts=None, statuses: bool = True,
-                                equations_only: bool = False):
+                                equations_only: bool = False, locate: str = "auto"):
         """verify_batch_pairs over up to BATCH_PAIRS_MANY_MAX pairs in one MSM
         (cpz_verify_batch_pairs_many): a tenant per entry, or a bulk batch over thousands of
         tenants.  Same arguments and the same (partial, batch_ok, status) as verify_batch_pairs;
         up to PAIRS_MAX pairs it is that call.  Above, a passing batch builds no table; a failing
         one with statuses=True is bisected and the ranges verified per proof build their pairs'
         tables PAIRS_MAX at a time.  pair_idx: n integers in [0, len(pairs)), checked here before
-        the library is called."""
+        the library is called.
+        locate: "auto" (bisection, then runs) or "partitioned" (CPZ_CALL_PARTITIONED_MANY: a
+        failing batch goes at once to the partitioned check over block-local pair lists, its
+        per-proof passes served by the call's small per-pair tables; up to PAIRS_MAX pairs it is
+        verify_batch_pairs' "partitioned").  Opt-in: nothing chooses it automatically."""
+        if locate not in ("auto", "partitioned"):
+            raise InvalidParams("locate must be \"auto\" or \"partitioned\", not %r" % (locate,))
+        flags = _flags(equations_only) | (_native.CALL_PARTITIONED_MANY if locate == "partitioned" else 0)
         n = len(y1)
         npairs = len(pairs)
         idx = _pair_indices(pair_idx, n, npairs)
@@ -652,7 +659,7 @@ class Gpu:
         ok = ctypes.c_int(0)
         out = np.empty(n, dtype=np.uint8) if statuses else None
         _native.check(self._lib.cpz_verify_batch_pairs_many(
-            self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
+            self._h, flags, npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
             _ptr(off), _ptr(present), bytes(seed), first_index, partial, ctypes.byref(ok), _ptr(out)))
         return partial.raw, bool(ok.value), out
 

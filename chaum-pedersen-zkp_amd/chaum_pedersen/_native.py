@@ -51,6 +51,7 @@ PROVE_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_PROVE_PAIRS_MAX_PROOFS: proofs per cpz_
 PROVE_PAIRS_MANY_MAX = 4096       # CPZ_PROVE_PAIRS_MANY_MAX: pairs per cpz_prove_pairs_many / _device call
 CALL_EQUATIONS_ONLY = 1   # CPZ_CALL_EQUATIONS_ONLY: commitment checks off for one call
 CALL_PARTITIONED = 2      # CPZ_CALL_PARTITIONED: cpz_verify_batch_pairs_ex searches a failing batch by blocks
+CALL_PARTITIONED_MANY = 4 # CPZ_CALL_PARTITIONED_MANY: cpz_verify_batch_pairs_many does, above PAIRS_MAX pairs
 BATCH_PAIRS_PART_MIN = 1 << 19   # CPZ_BATCH_PAIRS_PART_MIN: dense ranges from this size take the partitioned check
 NUM_STAGES = 16
 FALLBACK_STATS = 8

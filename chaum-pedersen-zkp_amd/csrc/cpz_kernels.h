@@ -289,8 +289,8 @@ hipError_t launch_verify_wide_pairs(const VerifyArgs& a, const ChallengeArgs& ca
 // a.status and pa.pair_idx are the whole batch's): a.status holds the prepare's decode-level
 // statuses, entries with a non-zero one keep it and every other ends with its per-proof status.
 // With pa.micro: every proof's [s'] B from its pair's small tables (radix-16 digits of s', two more
-// additions per window) and no descriptor's 128-entry tables read; listed blocks are not served
-// (hipErrorInvalidValue).
+// additions per window) and no descriptor's 128-entry tables read; listed blocks are served by an
+// instantiation of their own (the partitioned search of a batch over more than CPZ_PAIRS_MAX pairs).
 hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hipStream_t st);
 // The small tables of npairs pairs in one launch (k_pair_micro), from the generator words of
 // desc[p] into micro[p * kPairMicroInts ..]: a quad per (pair, generator).  A generator that does

@@ -1149,17 +1149,21 @@ hipError_t launch_prove_points_micro(const ProveArgs& a, const PairArgs& pa, hip
 // kMicro (k_verify_quad<false, true, true, true>, more than CPZ_PAIRS_MAX pairs in a call): the
 // generator term comes from the pair's small tables instead, pa.micro + pa.pair_idx[i] *
 // kPairMicroInts -- radix-16 digits of s', pair_micro_window in every window after the Y and R
-// additions -- and no descriptor's tab is read; listed blocks are not served (the launcher refuses
-// them).  A constant too: the other instantiations compile without it.
+// additions -- and no descriptor's tab is read.  A constant too: the other instantiations compile
+// without it.  kListed (k_verify_quad<false, true, true, true, true>): the small-table kernel over
+// listed blocks, with the decode-status skip of the listed kPairs form (the partitioned search of a
+// batch over more than CPZ_PAIRS_MAX pairs); an instantiation of its own, so that the unlisted
+// small-table kernel, cpz_verify_each_pairs_many's hot path, keeps its code.
 struct NoPairArgs {};
-template <bool kPre, bool kVar, bool kPairs = false, bool kMicro = false>
+template <bool kPre, bool kVar, bool kPairs = false, bool kMicro = false, bool kListed = !kMicro>
 __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditional_t<kPairs, PairArgs, NoPairArgs> pa) {
   static_assert(!kPairs || (kVar && !kPre), "mixed pairs: variable bases, rows decoded here");
   static_assert(!kMicro || kPairs, "small tables: mixed pairs only");
+  static_assert(kMicro || kListed, "only the small-table kernel has an unlisted-only form");
   const int t = threadIdx.x;
   int64_t i = (int64_t)blockIdx.x * 32 + (t >> 3);
   const int e = (t >> 2) & 1, q = t & 3;
-  if (!kMicro && a.blocks) {  // listed blocks of block_proofs proofs (the partitioned check's per-proof passes)
+  if (kListed && a.blocks) {  // listed blocks of block_proofs proofs (the partitioned check's per-proof passes)
     const int64_t lb = i / a.block_proofs;
     if (lb >= a.nblocks) return;
     i = (int64_t)a.blocks[lb] * a.block_proofs + i % a.block_proofs;
@@ -1168,7 +1172,7 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
   if (kPre && a.status[i] != kStOk) return;      // decode-level rejection: already final
   // listed blocks of a mixed-pair batch check (runtime.hip, pairs_part): the statuses are the
   // prepare's decode-level ones, final where non-zero; the others had a clean response status
-  if (kPairs && !kMicro && a.blocks && a.status[i] != kStOk) return;
+  if (kPairs && kListed && a.blocks && a.status[i] != kStOk) return;
 #if defined(CPZ_CLOCK_PROBE)
   // timing builds only: shader-clock stamps at the phase boundaries of block 0's first proof
   uint64_t stamp[kQuadPhases];
@@ -1327,16 +1331,20 @@ __global__ void __launch_bounds__(256) k_verify_quad(VerifyArgs a, std::conditio
 // blocks of a.block_proofs proofs each of a prepared mixed-pair batch (a.nblocks of them, at most
 // a.quad_max slots; rows, a.c, a.status and pa.pair_idx are the whole batch's, a.n its size) --
 // a.status holds the prepare's decode-level statuses and entries with a non-zero one keep it.
+// With pa.micro the generator terms come from the pairs' small tables, listed blocks included.
 hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hipStream_t st) {
   if (a.n <= 0 || (a.blocks && a.nblocks <= 0)) return hipSuccess;
   if (a.blocks && a.block_proofs < 1) return hipErrorInvalidValue;
   const int64_t slots = a.blocks ? a.nblocks * (int64_t)a.block_proofs : a.n;
   if (a.pre || !a.c || !a.status || !a.scratch || !pa.desc || !pa.pair_idx || slots > a.quad_max)
     return hipErrorInvalidValue;
-  if (pa.micro) {  // the pairs' small tables; no listed blocks
-    if (a.blocks) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_verify_quad<false, true, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a,
-                       pa);
+  if (pa.micro) {  // the pairs' small tables; listed blocks take the instantiation of their own
+    if (a.blocks)
+      hipLaunchKernelGGL((k_verify_quad<false, true, true, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0,
+                         st, a, pa);
+    else
+      hipLaunchKernelGGL((k_verify_quad<false, true, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a,
+                         pa);
     return hipGetLastError();
   }
   hipLaunchKernelGGL((k_verify_quad<false, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a, pa);

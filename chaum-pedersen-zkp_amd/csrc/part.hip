@@ -90,11 +90,22 @@ __device__ __forceinline__ sc scsum_reduce(const ScSum& a) {
 // indices staged in LDS (or reads, in the locate pass: PartArgs::pair_idx null).  A pair without an
 // entry in the block, or whose sum is 0, has zero digits and so no list entry.  kPairs is a
 // constant, so k_part_sort keeps its code.
+// kMany (k_part_sort_many, more than kPartMaxPairs pairs): the extras are keyed by block-local slot
+// (rlc.h).  Every thread parks its pair; the first thread holding a pair claims the slot equal to
+// the number of first holders below it, so the assignment depends on the block's indices alone
+// (the locate pass reads the table this pass wrote: the same slots).  Thread t then owns slot t,
+// both its extras (ids 4 kPartProofs + 2 t + k): it adds up both sums in registers before any digit
+// goes to sex, which takes all of sprod's bytes in this mode.  Also a constant: the other two
+// kernels keep their code.
 // ---------------------------------------------------------------------------------------
-template <bool kPairs>
+template <bool kPairs, bool kMany = false>
 __device__ __forceinline__ void part_sort_body(const PartArgs& a) {
+  static_assert(!kMany || kPairs, "many mode is a pair mode");
   constexpr int kT = kPartProofs;  // threads: one per proof of the block
-  constexpr int kListCap = kPairs ? kPartListCapPairs : kPartListCap;
+  constexpr int kListCap = kMany ? kPartListCapMany : kPairs ? kPartListCapPairs : kPartListCap;
+  constexpr int kExT = kMany ? 2 * kT : kT;  // sex's row length
+  static_assert(sizeof(int16_t) * kRlcWindows * kExT <= sizeof(sc) * 2 * kPartProofs, "sex fits sprod");
+  __shared__ uint16_t sslot[kMany ? kPartProofs : 1];     // (many mode only) slot -> pair
   __shared__ sc sprod[kPairs ? 2 * kPartProofs : 1];     // (pair mode only: unused, and so not
   __shared__ uint32_t spair[kPairs ? kPartProofs : 1];   //  allocated, without it)
   __shared__ uint32_t cur[kPartWindows][kPartBuckets];
@@ -109,11 +120,71 @@ __device__ __forceinline__ void part_sort_body(const PartArgs& a) {
   const int64_t j0 = 4 * pi;
   const bool in = pi < a.n;  // past the batch's end (last block): no entries
   int16_t ex[kRlcWindows];
-  const int nex = kPairs ? 2 * a.npairs : 2;  // threads holding an extra
+  const int nex = kMany ? kT : kPairs ? 2 * a.npairs : 2;  // threads holding an extra (many mode: two)
   // pair mode: extra t's digits, [window][thread], over the products once they are summed (a
   // dynamically indexed register array of them went to scratch)
   int16_t* sex = reinterpret_cast<int16_t*>(sprod);
-  if constexpr (kPairs) {
+  if constexpr (kMany) {
+    sc s0, s1;
+#pragma unroll
+    for (int k = 0; k < 8; k++) s0.w[k] = s1.w[k] = 0;
+    if (a.pair_idx) {
+      sprod[2 * t] = s0;  // past the end: zero, never read from a.prod
+      sprod[2 * t + 1] = s0;
+      if (in) {
+        sprod[2 * t] = a.prod[2 * pi];
+        sprod[2 * t + 1] = a.prod[2 * pi + 1];
+      }
+      const uint32_t mine = in ? a.pair_idx[pi] : 0xffffffffu;  // past the end: no pair
+      spair[t] = mine;
+      sslot[t] = kPartNoPair;
+      __syncthreads();
+      bool first = in;
+      for (int u = 0; u < t; u++) first = first && spair[u] != mine;
+      // the first holders below t, counted through flags parked in cur's first words (word t is
+      // this thread's own, zeroed above and again before the counts)
+      uint32_t* flag = &cur[0][0];
+      flag[t] = first ? 1u : 0u;
+      __syncthreads();
+      uint32_t rank = 0;
+      for (int u = 0; u < t; u++) rank += flag[u];
+      if (first) sslot[rank] = (uint16_t)mine;
+      __syncthreads();
+      flag[t] = 0;
+      a.slots[gb * kPartProofs + t] = sslot[t];
+      const uint32_t p = sslot[t];
+      if (p != kPartNoPair) {
+        ScSum acc0, acc1;
+#pragma unroll
+        for (int k = 0; k < 9; k++) acc0.w[k] = acc1.w[k] = 0;
+#pragma unroll 1
+        for (int u = 0; u < kT; u++)
+          if (spair[u] == p) {
+            scsum_add(acc0, sprod[2 * u]);
+            scsum_add(acc1, sprod[2 * u + 1]);
+          }
+        s0 = scsum_reduce(acc0);
+        s1 = scsum_reduce(acc1);
+      }
+      __syncthreads();  // every sum is in registers: sprod's bytes become sex
+    } else {
+      const uint16_t p = a.slots[(a.pmap ? (int64_t)a.pmap[gb] : gb) * kPartProofs + t];
+      sslot[t] = p;
+      if (p != kPartNoPair) {
+        s0 = a.prod[(2 * kPartProofs * gb + 2 * t)];
+        s1 = a.prod[(2 * kPartProofs * gb + 2 * t) + 1];
+      }
+    }
+    {
+      int16_t d[kRlcWindows];
+      recode16(d, s0.w);
+#pragma unroll
+      for (int w = 0; w < kRlcWindows; w++) sex[w * kExT + 2 * t] = d[w];
+      recode16(d, s1.w);
+#pragma unroll
+      for (int w = 0; w < kRlcWindows; w++) sex[w * kExT + 2 * t + 1] = d[w];
+    }
+  } else if constexpr (kPairs) {
     sc s;
 #pragma unroll
     for (int k = 0; k < 8; k++) s.w[k] = 0;
@@ -164,7 +235,15 @@ __device__ __forceinline__ void part_sort_body(const PartArgs& a) {
       if (lo) atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u);
       if (hi) atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u);
     }
-    if (t < nex) {
+    if constexpr (kMany) {
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        int lo, hi;
+        split8((int)sex[w * kExT + 2 * t + k], lo, hi);
+        if (lo) atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u);
+        if (hi) atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u);
+      }
+    } else if (t < nex) {
       int lo, hi;
       split8(kPairs ? (int)sex[w * kT + t] : (int)ex[w], lo, hi);
       if (lo) atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u);
@@ -255,7 +334,16 @@ __device__ __forceinline__ void part_sort_body(const PartArgs& a) {
       if (lo) list[atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u)] = id | (lo < 0 ? 0x8000 : 0);
       if (hi) list[atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u)] = id | (hi < 0 ? 0x8000 : 0);
     }
-    if (t < nex) {
+    if constexpr (kMany) {
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        int lo, hi;
+        split8((int)sex[w * kExT + 2 * t + k], lo, hi);
+        const uint16_t id = (uint16_t)(4 * kPartProofs + 2 * t + k);
+        if (lo) list[atomicAdd(&cur[2 * w][(lo < 0 ? -lo : lo) - 1], 1u)] = id | (lo < 0 ? 0x8000 : 0);
+        if (hi) list[atomicAdd(&cur[2 * w + 1][(hi < 0 ? -hi : hi) - 1], 1u)] = id | (hi < 0 ? 0x8000 : 0);
+      }
+    } else if (t < nex) {
       int lo, hi;
       split8(kPairs ? (int)sex[w * kT + t] : (int)ex[w], lo, hi);
       const uint16_t id = (uint16_t)(4 * kPartProofs + t);
@@ -267,6 +355,7 @@ __device__ __forceinline__ void part_sort_body(const PartArgs& a) {
 
 __global__ void __launch_bounds__(kPartProofs) k_part_sort(PartArgs a) { part_sort_body<false>(a); }
 __global__ void __launch_bounds__(kPartProofs) k_part_sort_pairs(PartArgs a) { part_sort_body<true>(a); }
+__global__ void __launch_bounds__(kPartProofs) k_part_sort_many(PartArgs a) { part_sort_body<true, true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // k_part_acc
@@ -292,13 +381,25 @@ __device__ __forceinline__ ge_p3 p3_select(const ge_p3& x, const ge_p3& y, bool 
 // current step's arithmetic runs, so the prefetch costs no VGPRs (the kernel sits at the
 // 256-VGPR budget of 2 waves per SIMD).  The vmcnt wait at the top of a step waits for that
 // prefetch and the id prefetch (and, once per lane, the stores of its first window's sums).
-// The only place that picks an extra's source: g / h of the tables, or (kPairs) the pairs' points.
-template <bool kPairs>
-__device__ __forceinline__ void part_stage(uint4 (*slot)[64], const PartArgs& a, const ge_niels* P, uint32_t id) {
+// The only place that picks an extra's source: g / h of the tables, or (kPairs) the pairs' points --
+// in many mode the points of the pair the block's table `stab` (k_part_sort_many; the prepared
+// block's under pmap) names for the id's slot.
+template <bool kPairs, bool kMany = false>
+__device__ __forceinline__ void part_stage(uint4 (*slot)[64], const PartArgs& a, const ge_niels* P, uint32_t id,
+                                           const uint16_t* stab = nullptr) {
   const uint32_t j = id & 0x7fffu;
-  const ge_niels* src = j < 4u * kPartProofs ? P + j
-                        : kPairs             ? a.gh + (j - 4u * kPartProofs)
-                                             : a.tab + (j == 4u * kPartProofs ? 0 : kNielsEntriesRlc);
+  const ge_niels* src;
+  if constexpr (kMany) {
+    src = P + j;
+    if (j >= 4u * kPartProofs) {
+      const uint32_t x = j - 4u * kPartProofs;  // 2 slot + k; the slot is in use, or it had no list entry
+      src = a.gh + (2u * stab[x >> 1] + (x & 1u));
+    }
+  } else {
+    src = j < 4u * kPartProofs ? P + j
+          : kPairs             ? a.gh + (j - 4u * kPartProofs)
+                               : a.tab + (j == 4u * kPartProofs ? 0 : kNielsEntriesRlc);
+  }
   const uint4* g = reinterpret_cast<const uint4*>(src);
 #pragma unroll
   for (int v = 0; v < 8; v++) __builtin_amdgcn_global_load_lds(g + v, &slot[v][0], 16, 0, 0);
@@ -337,7 +438,7 @@ __device__ __forceinline__ fe acc_load_z(uint4 (*az)[64], int lane) {
   return r;
 }
 
-template <bool kPairs>
+template <bool kPairs, bool kMany = false>
 __device__ __forceinline__ void part_acc_body(const PartArgs& a) {
   __shared__ uint4 lds[4][19][64];  // per wave: staged point (0..7), acc (8..15), acc's Z (16..18)
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -348,9 +449,11 @@ __device__ __forceinline__ void part_acc_body(const PartArgs& a) {
   const int64_t gb = a.blk0 + b;
   const uint32_t units = a.assign[b * kPartUnits + lane];  // (low unit, high unit), k_part_sort
   int v = (units & 0xff) >> 2, h = units & 3;
-  const uint16_t* list = a.lists + b * (kPairs ? kPartListCapPairs : kPartListCap);
+  const uint16_t* list = a.lists + b * (kMany ? kPartListCapMany : kPairs ? kPartListCapPairs : kPartListCap);
   const uint16_t* ob = a.offs + b * kPartOffs;
-  const ge_niels* P = a.pts + (int64_t)4 * kPartProofs * (a.pmap ? (int64_t)a.pmap[gb] : gb);
+  const int64_t pb = a.pmap ? (int64_t)a.pmap[gb] : gb;  // the prepared block
+  const ge_niels* P = a.pts + (int64_t)4 * kPartProofs * pb;
+  const uint16_t* stab = kMany ? a.slots + pb * kPartProofs : nullptr;
   ge_p3* ws = a.wsum + gb * kPartWsum;  // indexed by the global block: one combine pass for all chunks
   uint4 (*slot)[64] = lds[wv];
   int width = part_width(v), klo = width * h, k = klo;
@@ -358,7 +461,7 @@ __device__ __forceinline__ void part_acc_body(const PartArgs& a) {
   uint32_t e = o[k], eend = o[k + 1], elast = o[klo + width];
   uint32_t cid = e < elast ? list[e] : 0u;
   uint32_t nid = e + 1 < elast ? list[e + 1] : 0u;
-  if (e < eend) part_stage<kPairs>(slot, a, P, cid);
+  if (e < eend) part_stage<kPairs, kMany>(slot, a, P, cid, stab);
   ge_p3 run = ge_identity();
   uint4 (*an)[64] = lds[wv] + 8;   // acc's Y+X, Y-X, 2dT (the staged points' layout)
   uint4 (*az)[64] = lds[wv] + 16;  // acc's Z
@@ -410,7 +513,7 @@ __device__ __forceinline__ void part_acc_body(const PartArgs& a) {
       k2 = k + 1;
       eend2 = o[k2 + 1];
     }
-    if (!wend && e2 < eend2) part_stage<kPairs>(slot, a, P, cid2);
+    if (!wend && e2 < eend2) part_stage<kPairs, kMany>(slot, a, P, cid2, stab);
     {
       ge_cached oc;
       oc.YpX = q.ypx;
@@ -440,7 +543,7 @@ __device__ __forceinline__ void part_acc_body(const PartArgs& a) {
       elast = o[klo + width];
       cid2 = e2 < elast ? list[e2] : 0u;
       nid2 = e2 + 1 < elast ? list[e2 + 1] : 0u;
-      if (e2 < eend2) part_stage<kPairs>(slot, a, P, cid2);
+      if (e2 < eend2) part_stage<kPairs, kMany>(slot, a, P, cid2, stab);
       run = ge_identity();
       acc_store(an, az, lane, ge_cached_identity());
     }
@@ -454,6 +557,7 @@ __device__ __forceinline__ void part_acc_body(const PartArgs& a) {
 
 __global__ void __launch_bounds__(256, 2) k_part_acc(PartArgs a) { part_acc_body<false>(a); }
 __global__ void __launch_bounds__(256, 2) k_part_acc_pairs(PartArgs a) { part_acc_body<true>(a); }
+__global__ void __launch_bounds__(256, 2) k_part_acc_many(PartArgs a) { part_acc_body<true, true>(a); }
 
 // ---------------------------------------------------------------------------------------
 // k_part_combine: quad j of the wave owns block 16 x blockIdx + j.
@@ -646,7 +750,9 @@ __device__ __forceinline__ void index_weight_digits(int16_t d[kRlcWindows], cons
 // kPairs (k_part_index_digits_pairs): the same digits; the sums are per pair -- thread t parks
 // j_t prod[2 i], j_t prod[2 i + 1] (the prepare's products: zero where it gave zero weight) and its
 // pair in LDS, thread u < 2 npairs adds up extra u's and writes it to pair_sums, compact.
-template <bool kPairs>
+// kMany (k_part_index_digits_many): the sums are by the prepared block's slots instead -- thread s
+// adds up both sums of the pair the first pass's table names for slot s (zero for an unused slot).
+template <bool kPairs, bool kMany = false>
 __device__ __forceinline__ void part_index_digits_body(const PartIdxArgs& a) {
   static_assert(kPartLocJ0 < (1 << 16) - 258 && kPartLocJ0 - 2 * (kPartProofs - 1) > (1 << 15),
                 "index multipliers: digit 8 of j a below 2^15 - 128, and above 2^15 so that it spreads");
@@ -695,7 +801,23 @@ __device__ __forceinline__ void part_index_digits_body(const PartIdxArgs& a) {
     for (int w = 0; w < kRlcWindows; w++) a.digits[(int64_t)w * a.dstride + 4 * o + q] = d[w];
   }
   __syncthreads();
-  if constexpr (kPairs) {
+  if constexpr (kMany) {
+    const uint32_t p = a.slots[(int64_t)a.blocks[b] * kPartProofs + t];
+    ScSum acc0, acc1;
+#pragma unroll
+    for (int k = 0; k < 9; k++) acc0.w[k] = acc1.w[k] = 0;
+    if (p != kPartNoPair) {
+#pragma unroll 1
+      for (int u = 0; u < kPartProofs; u++)
+        if (spair[u] == p) {
+          scsum_add(acc0, red_a[u]);
+          scsum_add(acc1, red_b[u]);
+        }
+    }
+    a.pair_sums[2 * o] = scsum_reduce(acc0);
+    a.pair_sums[2 * o + 1] = scsum_reduce(acc1);
+    return;
+  } else if constexpr (kPairs) {
     if (t < 2 * a.npairs) {
       const uint32_t p = (uint32_t)t >> 1;
       const sc* red = (t & 1) ? red_b : red_a;
@@ -726,6 +848,9 @@ __device__ __forceinline__ void part_index_digits_body(const PartIdxArgs& a) {
 __global__ void __launch_bounds__(kPartProofs) k_part_index_digits(PartIdxArgs a) { part_index_digits_body<false>(a); }
 __global__ void __launch_bounds__(kPartProofs) k_part_index_digits_pairs(PartIdxArgs a) {
   part_index_digits_body<true>(a);
+}
+__global__ void __launch_bounds__(kPartProofs) k_part_index_digits_many(PartIdxArgs a) {
+  part_index_digits_body<true, true>(a);
 }
 
 // [k] P for a small k > 0 (double and add from the top bit).
@@ -781,7 +906,11 @@ __global__ void __launch_bounds__(256) k_gather_status(const uint8_t* status, co
 
 hipError_t launch_part_index_digits(const PartIdxArgs& a, hipStream_t st) {
   if (a.nblk <= 0) return hipSuccess;
-  if (a.prod) {
+  if (a.slots) {  // many mode
+    if (!a.prod || !a.pair_idx || !a.pair_sums || a.npairs < 1 || a.npairs > kPairBucketMaxPairs)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_part_index_digits_many, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  } else if (a.prod) {
     if (!a.pair_idx || !a.pair_sums || a.npairs < 1 || a.npairs > kPartMaxPairs) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_part_index_digits_pairs, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
   } else {
@@ -806,7 +935,11 @@ hipError_t launch_gather_status(const uint8_t* status, const uint32_t* idx, int6
 
 hipError_t launch_part_sort(const PartArgs& a, hipStream_t st) {
   if (a.nblk <= 0) return hipSuccess;
-  if (a.prod) {
+  if (a.slots) {  // many mode; the locate pass (null pair_idx) reads the prepared blocks' rows through pmap
+    if (!a.prod || !a.gh || a.npairs < 1 || a.npairs > kPairBucketMaxPairs || (!a.pair_idx && !a.pmap))
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_part_sort_many, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
+  } else if (a.prod) {
     if (!a.gh || a.npairs < 1 || a.npairs > kPartMaxPairs) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_part_sort_pairs, dim3((unsigned)a.nblk), dim3(kPartProofs), 0, st, a);
   } else {
@@ -817,7 +950,10 @@ hipError_t launch_part_sort(const PartArgs& a, hipStream_t st) {
 
 hipError_t launch_part_acc(const PartArgs& a, hipStream_t st) {
   if (a.nblk <= 0) return hipSuccess;
-  if (a.prod)
+  if (a.slots) {
+    if (!a.prod || !a.gh || a.npairs < 1 || a.npairs > kPairBucketMaxPairs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_part_acc_many, dim3((unsigned)((a.nblk + 3) / 4)), dim3(256), 0, st, a);
+  } else if (a.prod)
     hipLaunchKernelGGL(k_part_acc_pairs, dim3((unsigned)((a.nblk + 3) / 4)), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(k_part_acc, dim3((unsigned)((a.nblk + 3) / 4)), dim3(256), 0, st, a);

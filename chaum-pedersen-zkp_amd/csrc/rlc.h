@@ -126,6 +126,20 @@ constexpr int kPartListCapPairs = kPartWindows * (4 * kPartProofs + 2 * kPartMax
 static_assert(kPartListCapPairs <= 0xffff, "pair mode: a block's list offsets are 16-bit");
 static_assert(4 * kPartProofs + 2 * kPartMaxPairs <= 0x8000, "pair mode: point ids take 15 bits (bit 15: negate)");
 static_assert(2 * kPartMaxPairs <= kPartProofs, "pair mode: one sort thread per extra");
+// Many mode (PartArgs::slots, more than kPartMaxPairs pairs in the batch): a block's extras are
+// keyed by block-local slot, a pair's slot being its rank by first occurrence among the block's
+// proofs -- at most kPartProofs slots whatever the batch's pair count.  Extra id
+// 4 kPartProofs + 2 slot + k is gh[2 pair(slot) + k]; the block's slot -> pair table is 16-bit
+// (kPartNoPair: the slot is unused), and its launches have a list stride of their own.
+constexpr int kPartListCapMany = kPartWindows * (4 * kPartProofs + 2 * kPartProofs);
+constexpr uint16_t kPartNoPair = 0xffff;
+constexpr bool part_many_fits(int proofs) {
+  return kPartWindows * (4 * proofs + 2 * proofs) <= 0xffff && 4 * proofs + 2 * proofs <= 0x8000;
+}
+static_assert(part_many_fits(128) && part_many_fits(256),
+              "many mode: 16-bit list offsets and 15-bit point ids (bit 15: negate) for blocks of 128 and 256 proofs");
+static_assert(kPartListCapMany <= 0xffff, "many mode: a block's list offsets are 16-bit");
+static_assert(4 * kPartProofs + 2 * kPartProofs <= 0x8000, "many mode: point ids take 15 bits (bit 15: negate)");
 constexpr int kPartOffs = kPartWindows * (kPartBuckets + 1);
 constexpr int kPartWsum = kPartWindows * kPartQuarters * 2;  // (W, S) per window and quarter
 constexpr int kPartUnits = kPartWindows * kPartQuarters / 2;  // walk units per half (64 = lanes)
@@ -174,6 +188,13 @@ struct PartArgs {
   const uint32_t* pair_idx = nullptr;  // [n]
   const ge_niels* gh = nullptr;        // pair p's affine Niels points at gh[2 p], gh[2 p + 1] (k_pair_setup)
   int npairs = 0;
+  // Many mode (pair mode with slots set; npairs up to kPairBucketMaxPairs): lists has a stride of
+  // kPartListCapMany and block b's extras are gh[2 slots[b][s] + k] (id 4 kPartProofs + 2 s + k) with
+  // the sum mod l of prod[2 i + k] over the block's proofs i < n under that pair.  With pair_idx the
+  // sort assigns the slots (first occurrence) and writes block blk0 + b's row of the table; with
+  // null pair_idx (the locate pass) it reads the row of prepared block pmap[blk0 + b], and prod
+  // holds the sums by slot, [blocks][kPartProofs][2], compact (k_part_index_digits_many).
+  uint16_t* slots = nullptr;           // [blocks][kPartProofs] slot -> pair, kPartNoPair where unused
 };
 
 // ---- locating a failing block's forged entry (part.hip) ----------------------------------
@@ -214,6 +235,10 @@ struct PartIdxArgs {
   const uint32_t* pair_idx = nullptr;  // [n]
   int npairs = 0;
   sc* pair_sums = nullptr;             // [nblk][npairs][2], compact
+  // Many mode (slots set): the sums are by the prepared block's slots -- listed block b's sums over
+  // its proofs under pair slots[blocks[b]][s] go to pair_sums[(b kPartProofs + s) 2 + k], zero for an
+  // unused slot.
+  const uint16_t* slots = nullptr;     // [prepared blocks][kPartProofs], as the first pass's sort wrote it
 };
 
 struct PartLocArgs {
@@ -265,6 +290,7 @@ struct RlcPairExtra {
 // start / ustart above; `cursor` is scratch of npairs + 1 words.  The order inside a pair's list
 // is not fixed, which does not matter: addition mod l is exact.  npairs <= kPairBucketMaxPairs.
 constexpr int kPairBucketMaxPairs = 4096;
+static_assert(kPairBucketMaxPairs <= kPartNoPair, "many mode: a block's slot -> pair table holds 16-bit pair indices");
 hipError_t launch_pair_bucket(const uint32_t* pair_idx, int64_t n, int npairs, uint32_t* list, uint32_t* start,
                               uint32_t* ustart, uint32_t* cursor, hipStream_t st);
 // The extras alone (what launch_rlc_msm runs first for a px with lists): points e0 + 2 p,

@@ -332,6 +332,7 @@ struct cpz_ctx {
   // blocks, every block's partial and fail flag, the sum's scratch, the failing-block list
   DevBuf pt_lists, pt_offs, pt_wsum, pt_part, pt_fail, pt_tmp, pt_blocks, pt_assign;
   DevBuf pt_ldig, pt_lsum, pt_lpart, pt_lfail, pt_loc;  // the locate pass over failing blocks
+  DevBuf pt_slots;  // many mode (pairs_many_part): every block's slot -> pair table
   // what the last batch call's fallback did (cpz_ctx_fallback_stats)
   uint64_t fb_stats[CPZ_FALLBACK_STATS] = {};
   // commitment checks (statuses 4 and 5: the Proof::from_bytes rejections); off = equations only.
@@ -1441,7 +1442,7 @@ int part_reserve(cpz_ctx* ctx, int64_t n) {
 void part_release_blocks(cpz_ctx* ctx) {
   for (DevBuf* b : {&ctx->pt_lists, &ctx->pt_offs, &ctx->pt_wsum, &ctx->pt_part, &ctx->pt_fail, &ctx->pt_tmp,
                     &ctx->pt_blocks, &ctx->pt_assign, &ctx->pt_ldig, &ctx->pt_lsum, &ctx->pt_lpart, &ctx->pt_lfail,
-                    &ctx->pt_loc})
+                    &ctx->pt_loc, &ctx->pt_slots})
     b->release();
   (void)hipGetLastError();
 }
@@ -1459,7 +1460,8 @@ void part_release(cpz_ctx* ctx) {
 // every failing block is verified per proof, as without the pass.
 // px (a range of a mixed-pair batch, pairs_part): the prepared points, challenges, products and
 // indices of the range (n, s, d_status and first_index are the range's too, blocks count from its
-// start), and the sums are per pair (PartIdxArgs::pair_sums -> PartArgs::prod).
+// start), and the sums are per pair (PartIdxArgs::pair_sums -> PartArgs::prod).  With slots (many
+// mode, pairs_many_part): the first pass's slot tables, and the sums are by slot.
 struct PartPairs {
   const cpz::ge_niels* pts;
   const uint32_t* c;
@@ -1467,6 +1469,7 @@ struct PartPairs {
   const uint32_t* pair_idx;
   const cpz::ge_niels* gh;
   int npairs;
+  uint16_t* slots = nullptr;
 };
 
 int part_locate(cpz_ctx* ctx, int64_t n, const uint32_t* s, const uint8_t* d_status, const uint8_t seed[32],
@@ -1474,7 +1477,7 @@ int part_locate(cpz_ctx* ctx, int64_t n, const uint32_t* s, const uint8_t* d_sta
                 std::vector<uint32_t>& cand, hipStream_t st, const PartPairs* px = nullptr) {
   const int64_t nf = (int64_t)blocks.size();
   const int64_t dstride = ((4 * cpz::kPartProofs * nf) + 7) & ~(int64_t)7;
-  const int64_t nsum = px ? nf * px->npairs : nf * (cpz::kPartProofs / cpz::kRlcSumBlock);
+  const int64_t nsum = px ? nf * (px->slots ? cpz::kPartProofs : px->npairs) : nf * (cpz::kPartProofs / cpz::kRlcSumBlock);
   if (ctx->pt_ldig.ensure((size_t)cpz::kRlcWindows * dstride * sizeof(int16_t)) != hipSuccess ||
       ctx->pt_lsum.ensure((size_t)2 * nsum * sizeof(cpz::sc)) != hipSuccess ||
       ctx->pt_lpart.ensure((size_t)nf * sizeof(cpz::ge_p3)) != hipSuccess ||
@@ -1503,6 +1506,7 @@ int part_locate(cpz_ctx* ctx, int64_t n, const uint32_t* s, const uint8_t* d_sta
       ia.pair_idx = px->pair_idx;
       ia.npairs = px->npairs;
       ia.pair_sums = ia.block_sums;
+      ia.slots = px->slots;
     }
     CPZ_HIP(cpz::launch_part_index_digits(ia, st));
     cpz::PartArgs pa;
@@ -1516,6 +1520,7 @@ int part_locate(cpz_ctx* ctx, int64_t n, const uint32_t* s, const uint8_t* d_sta
       pa.prod = ia.pair_sums;
       pa.gh = px->gh;
       pa.npairs = px->npairs;
+      pa.slots = px->slots;  // many mode: the prepared blocks' rows, read through pmap
     } else {
       pa.tab = static_cast<const cpz::ge_niels*>(ctx->gs->tab.p);
     }
@@ -2282,7 +2287,7 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
   ctx->rl_span_ident.release();
   for (DevBuf* b : {&ctx->pt_lists, &ctx->pt_offs, &ctx->pt_wsum, &ctx->pt_part, &ctx->pt_fail, &ctx->pt_tmp,
                     &ctx->pt_blocks, &ctx->pt_assign, &ctx->pt_ldig, &ctx->pt_lsum, &ctx->pt_lpart, &ctx->pt_lfail,
-                    &ctx->pt_loc})
+                    &ctx->pt_loc, &ctx->pt_slots})
     b->release();
   ctx->rl_flags.release();
   ctx->rl_parts.release();
@@ -3086,8 +3091,9 @@ int pairs_verify_range(cpz_ctx* ctx, PairBatch& b, int64_t lo, int64_t hi, hipSt
 // proofs each of the prepared batch, d_list on the device: launches of at most verify_quad_max(ctx)
 // slots, alternating over the verify streams and their slabs (launch_quad_pairs_chunks).  The
 // challenges are the batch's (ctx->c); entries with a non-zero decode-level status keep it.
+// micro (pairs_many_part): the call's small tables, read instead of the descriptors' 128-entry ones.
 int pairs_verify_listed(cpz_ctx* ctx, const PairBatch& b, const uint32_t* d_list, int64_t nb, int block_proofs,
-                        hipStream_t st) {
+                        hipStream_t st, const int32_t* micro = nullptr) {
   if (nb <= 0) return CPZ_OK;
   const int64_t per = verify_quad_max(ctx) / block_proofs;  // listed blocks per launch
   if (per < 1) return fail(CPZ_EINVAL, "internal: no room for the eight-lane kernel's tables");
@@ -3108,6 +3114,7 @@ int pairs_verify_listed(cpz_ctx* ctx, const PairBatch& b, const uint32_t* d_list
   cpz::PairArgs pa;
   pa.desc = b.d_full;
   pa.pair_idx = b.d_idx;
+  pa.micro = micro;
   for (int64_t c = 0; c < chunks; c++) {
     const int k = (int)(c % nst);  // stream k owns scratch slab k
     hipStream_t sc = k == 0 ? st : ctx->aux_stream[k - 1];
@@ -3447,11 +3454,97 @@ int pairs_bucket(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
   return CPZ_OK;
 }
 
+// The partitioned search over a whole failing batch of more than CPZ_PAIRS_MAX pairs
+// (CPZ_CALL_PARTITIONED_MANY): pairs_part with block-local pair slots (part.hip's many mode) and
+// every per-proof pass from the call's small tables (k_pair_micro, ctx->ep_micro: one launch, one
+// stage-13 span that counts the pairs).  No 128-entry set is built, no run is formed and the
+// light-set cache is not touched.  More than half of the blocks failing: the whole batch goes
+// through cpz_verify_each_pairs_many's chunked eight-lane path.
+int pairs_many_part(cpz_ctx* ctx, PairBatch& b, hipStream_t st) {
+  const int64_t n = b.n;
+  const int64_t nblk = (n + cpz::kPartProofs - 1) / cpz::kPartProofs;
+  CPZ_HIP(ctx->ep_micro.ensure(b.npairs * (size_t)cpz::kPairMicroBytes));
+  const int32_t* micro = static_cast<const int32_t*>(ctx->ep_micro.p);
+  {
+    StageTimer timer(ctx, 13, st);
+    timer.count = (int)b.npairs;
+    CPZ_HIP(cpz::launch_pair_micro(b.d_desc, (int)b.npairs, static_cast<int32_t*>(ctx->ep_micro.p), st));
+  }
+  CPZ_HIP(ctx->pt_lists.ensure((size_t)nblk * cpz::kPartListCapMany * sizeof(uint16_t)));
+  CPZ_HIP(ctx->pt_slots.ensure((size_t)nblk * cpz::kPartProofs * sizeof(uint16_t)));
+  CPZ_HIP(ctx->pt_assign.ensure((size_t)nblk * cpz::kPartUnits * sizeof(uint16_t)));
+  CPZ_HIP(ctx->pt_offs.ensure((size_t)nblk * cpz::kPartOffs * sizeof(uint16_t)));
+  CPZ_HIP(ctx->pt_wsum.ensure((size_t)nblk * cpz::kPartWsum * sizeof(cpz::ge_p3)));
+  CPZ_HIP(ctx->pt_part.ensure((size_t)nblk * sizeof(cpz::ge_p3)));
+  CPZ_HIP(ctx->pt_fail.ensure((size_t)nblk));
+  CPZ_HIP(ctx->pt_blocks.ensure((size_t)2 * nblk * sizeof(uint32_t)));
+  PartPairs px;
+  px.pts = static_cast<const cpz::ge_niels*>(ctx->rl_prep.pts.p);
+  px.c = static_cast<const uint32_t*>(ctx->c.p);
+  px.prod = static_cast<const cpz::sc*>(ctx->rl_prep.prod.p);
+  px.pair_idx = b.d_idx;
+  px.gh = static_cast<const cpz::ge_niels*>(ctx->bp_pts.p);
+  px.npairs = (int)b.npairs;
+  px.slots = static_cast<uint16_t*>(ctx->pt_slots.p);
+  {
+    cpz::PartArgs pa;
+    pa.n = n;
+    pa.pts = px.pts;
+    pa.digits = static_cast<const int16_t*>(ctx->rl_prep.dig.p);
+    pa.dstride = rlc_dstride(ctx->rl_prep.cap);
+    pa.prod = px.prod;
+    pa.pair_idx = px.pair_idx;
+    pa.gh = px.gh;
+    pa.npairs = px.npairs;
+    pa.slots = px.slots;
+    pa.lists = static_cast<uint16_t*>(ctx->pt_lists.p);
+    pa.assign = static_cast<uint16_t*>(ctx->pt_assign.p);
+    pa.offs = static_cast<uint16_t*>(ctx->pt_offs.p);
+    pa.wsum = static_cast<cpz::ge_p3*>(ctx->pt_wsum.p);
+    pa.part = static_cast<cpz::ge_p3*>(ctx->pt_part.p);
+    pa.fail = static_cast<uint8_t*>(ctx->pt_fail.p);
+    pa.blk0 = 0;
+    pa.nblk = nblk;
+    StageTimer t(ctx, 3, st);
+    CPZ_HIP(cpz::launch_part_sort(pa, st));
+    {
+      StageTimer ta(ctx, 14, st);
+      CPZ_HIP(cpz::launch_part_acc(pa, st));
+    }
+    CPZ_HIP(cpz::launch_part_combine(pa, st));
+  }
+  std::vector<uint32_t> blocks;
+  if (int rc = part_failing_blocks(ctx, nblk, blocks, st)) return rc;
+  if (blocks.empty()) return CPZ_OK;
+  if (2 * (int64_t)blocks.size() > nblk) {  // dense: everything per proof, from the small tables
+    ctx->fb_stats[4] += (uint64_t)n;
+    PairRange r;
+    r.rows = b.rows;
+    r.cx = b.cx;
+    r.idx = b.d_idx;
+    r.desc = b.d_desc;
+    r.micro = micro;
+    r.c = static_cast<uint32_t*>(ctx->c.p);  // rewritten with the same values
+    r.status = b.d_status;
+    return launch_quad_pairs_chunks(ctx, r, 0, n, 4, st);
+  }
+  CPZ_HIP(hipMemcpyAsync(ctx->pt_blocks.p, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  std::vector<uint32_t> whole = blocks, cand;
+  if (CPZ_PART_LOCATE) {
+    int rc = part_locate(ctx, n, b.rows.s, b.d_status, b.seed, b.first_index, blocks, whole, cand, st, &px);
+    if (rc) return rc;
+  }
+  return part_verify_lists(ctx, n, 0, b.d_status, blocks.size(), whole, cand, st,
+                           [&](const uint32_t* d_list, int64_t nb, int block_proofs) {
+                             return pairs_verify_listed(ctx, b, d_list, nb, block_proofs, st, micro);
+                           });
+}
+
 // cpz_verify_batch_pairs_ex (max_pairs = CPZ_PAIRS_MAX) and, for more pairs than that,
 // cpz_verify_batch_pairs_many (CPZ_BATCH_PAIRS_MANY_MAX).  More than CPZ_PAIRS_MAX pairs: the
 // descriptors are built on the device, the per-pair sums come from the bucketed lists, and a
 // failing batch is bisected down to runs (CPZ_CALL_PARTITIONED is ignored: part.hip's lists hold
-// CPZ_PAIRS_MAX pairs).
+// CPZ_PAIRS_MAX pairs) -- or, with CPZ_CALL_PARTITIONED_MANY, searched by pairs_many_part.
 int verify_batch_pairs_impl(cpz_ctx* ctx, uint32_t flags, size_t max_pairs, const char* pairs_bound, size_t npairs,
                             const uint8_t* pairs, size_t n, const uint32_t* pair_idx, const uint8_t* y1,
                             const uint8_t* y2, const uint8_t* r1, const uint8_t* r2, const uint8_t* s,
@@ -3537,6 +3630,9 @@ int verify_batch_pairs_impl(cpz_ctx* ctx, uint32_t flags, size_t max_pairs, cons
     if (!many && (flags & CPZ_CALL_PARTITIONED)) {  // the caller knows its density: no bisection
       ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
       rc = pairs_part(ctx, b, 0, b.n, st);
+    } else if (many && (flags & CPZ_CALL_PARTITIONED_MANY)) {  // the same above CPZ_PAIRS_MAX pairs
+      ctx->fb_stats[0] = CPZ_FALLBACK_PARTITIONED;
+      rc = pairs_many_part(ctx, b, st);
     } else {
       ctx->fb_stats[0] = CPZ_FALLBACK_BISECTION;
       rc = many ? pairs_many_fallback(ctx, b, st) : pairs_fallback(ctx, b, st);
@@ -3581,6 +3677,9 @@ int cpz_verify_batch_pairs_many(cpz_ctx* ctx, uint32_t flags, size_t npairs, con
                                 uint8_t partial_out[32], int* batch_ok, uint8_t* status_out) {
   // up to CPZ_PAIRS_MAX pairs this is cpz_verify_batch_pairs_ex itself: same route, same timing
   const bool many = npairs > CPZ_PAIRS_MAX;
+  // "partitioned" means one thing to a caller at any npairs: forwarded, the many flag is the plain one
+  if (!many && (flags & CPZ_CALL_PARTITIONED_MANY))
+    flags = (flags & ~CPZ_CALL_PARTITIONED_MANY) | CPZ_CALL_PARTITIONED;
   return verify_batch_pairs_impl(ctx, flags, many ? CPZ_BATCH_PAIRS_MANY_MAX : CPZ_PAIRS_MAX,
                                  many ? "CPZ_BATCH_PAIRS_MANY_MAX" : "CPZ_PAIRS_MAX", npairs, pairs, n, pair_idx, y1, y2,
                                  r1, r2, s, ctx_bytes, ctx_off, ctx_present, seed, first_index, partial_out, batch_ok,

@@ -97,6 +97,17 @@ int cpz_ctx_set_commitment_checks(cpz_ctx *ctx, int enable);
  *                            its size, instead of by bisection -- for callers who know that
  *                            their invalid entries are too many for bisection to prune. */
 #define CPZ_CALL_PARTITIONED 2u
+/*   CPZ_CALL_PARTITIONED_MANY  cpz_verify_batch_pairs_many alone (every other entry point ignores
+ *                            it): above CPZ_PAIRS_MAX pairs a failing batch with status_out is
+ *                            searched by the partitioned check over block-local pair lists, with
+ *                            every per-proof pass from the call's small per-pair tables, instead
+ *                            of by bisection and runs; up to CPZ_PAIRS_MAX pairs the forwarded
+ *                            call sees CPZ_CALL_PARTITIONED in its place.  Opt-in, not automatic.
+ *                            2^20 entries over 4096 pairs with 0.1 % forged: 29.1 ms against
+ *                            13.4 s unflagged and 59.7 ms for cpz_verify_each_pairs_many; from
+ *                            1 % forged it loses to the latter (79.3 against 59.0 ms), as it
+ *                            does below ~2^17 entries: see cpz_verify_batch_pairs_many. */
+#define CPZ_CALL_PARTITIONED_MANY 4u
 
 /* Thread-local description of the last error returned on this thread. */
 const char *cpz_last_error(void);
@@ -513,6 +524,31 @@ int cpz_verify_batch_pairs_ex(cpz_ctx *ctx, uint32_t flags, size_t npairs, const
  *   - CPZ_CALL_PARTITIONED is ignored: the partitioned check's lists hold CPZ_PAIRS_MAX pairs,
  *     so the route is bisection, then runs;
  *   - cpz_ctx_fallback_stats reports CPZ_FALLBACK_NONE or _BISECTION with out[4] and out[5].
+ *   - CPZ_CALL_PARTITIONED_MANY (opt-in) sends a failing batch with status_out to the partitioned
+ *     search at once instead: every pair's small tables in one launch (one stage-13 span whose
+ *     launch count is npairs, as in cpz_verify_each_pairs_many), every 128-entry block's partial
+ *     with the block's pairs in block-local slots (a pair's slot is its rank by first occurrence
+ *     in the block, at most 128 of them whatever npairs is), the failing blocks' index-weighted
+ *     partials, and per-proof verification from the small tables of the located entries and of
+ *     the blocks not located (more than half of the blocks failing: of the whole batch).  No
+ *     128-entry set is built, no run is formed, the light-set cache and its LRU order are
+ *     untouched and stage 7 stays zero; partial_out, batch_ok and every status are as without
+ *     the flag, and shards still combine.  cpz_ctx_fallback_stats then reports
+ *     CPZ_FALLBACK_PARTITIONED with out[2] .. out[7] as for cpz_verify_batch_pairs_ex, out[1] = 0
+ *     (no sample) and out[5] = 0.  A passing batch, or one without status_out, is unaffected.
+ *     The route is not automatic: neither a size or density threshold nor a sampled guard like
+ *     cpz_verify_batch_pairs_ex's chooses it unasked; both wait for measurements
+ *     (tools/batch_pairs_many_part_ab.py writes profiles/batch_pairs_many_part_ab.json).
+ *     Measured on an MI355X over 4096 pairs, flagged / unflagged / cpz_verify_each_pairs_many on
+ *     the same rows, medians in ms: 2^20 entries, 1 forged 27.5 / 38.0 / 59.6; 0.1 % forged
+ *     29.1 / 13,357 / 59.7; 1 % and 10 % forged (most blocks fail, everything is verified per
+ *     proof after the block pass) 79.3-79.7 / 13,235-13,258 / 59.0-59.1 -- the route loses to
+ *     cpz_verify_each_pairs_many there.  With 90 % of the entries in one pair: 24.2 / 35.9 /
+ *     59.0, 25.8 / 1,719 / 59.0, 76.0-76.6 / 1,720-1,794 / 59.2-59.7.  2^17 entries: 1 forged
+ *     8.2 / 20.3 / 8.4, 0.1 % 9.1 / 1,662 / 8.7, 1 % and 10 % 12.6 / 1,660-1,666 / 8.7 (skewed:
+ *     7.5 / 17.1 / 8.6, 8.3 / 221 / 8.6, 12.0-12.1 / 220 / 8.5) -- no gain over
+ *     cpz_verify_each_pairs_many at that size, and a loss from 1 %.  1000 entries over 1000
+ *     pairs, 3 forged: 5.9 / 13.2 / 0.90 -- cpz_verify_each_pairs_many is the call to make.
  * Checked before anything is staged, in cpz_verify_batch_pairs_ex's order and wording,
  * cpz_last_error naming the lowest offending pair or entry, and no output buffer is written on
  * an error; npairs > CPZ_BATCH_PAIRS_MANY_MAX -> CPZ_EINVAL.  Host buffers only. */

@@ -49,6 +49,7 @@ pub const CPZ_NUM_STAGES: usize = 16;
 pub const CPZ_ABI_VERSION: c_int = 5;
 pub const CPZ_CALL_EQUATIONS_ONLY: u32 = 1;
 pub const CPZ_CALL_PARTITIONED: u32 = 2;
+pub const CPZ_CALL_PARTITIONED_MANY: u32 = 4;
 pub const CPZ_PAIRS_MAX: usize = 64;
 pub const CPZ_PAIRS_MAX_PROOFS: usize = 2048;
 pub const CPZ_BATCH_PAIRS_MAX_PROOFS: usize = 1048576;
