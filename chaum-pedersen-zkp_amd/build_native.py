@@ -95,7 +95,7 @@ UNIT_FLAGS = {"wide.hip": ["-falign-loops=64"]}
 def build_libcpz(force: bool = False, verbose: bool = False, out: str = LIBCPZ, defines=()) -> str:
     """Build the product library.  `out` / `defines` build a tuning variant (e.g.
     CPZ_VERIFY_WAVES=3) elsewhere, for side-by-side measurement with CPZ_LIB=<out>."""
-    units = ["kernels.hip", "wide.hip", "rlc.hip", "part.hip", "runtime.hip"]
+    units = ["kernels.hip", "wide.hip", "rlc.hip", "part.hip", "h2g.hip", "runtime.hip"]
     srcs = [os.path.join(CSRC, u) for u in units] + _headers()
     if not force and not defines and not _newer(out, srcs):
         return out
@@ -140,7 +140,8 @@ def build_hosttest(force: bool = False, out: str = HOSTTEST, defines=()) -> str:
     the CPU tests can hold the fallback code to the same checks."""
     srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("hostlib.cpp", "hostlib_joint.cpp", "hostlib_lean.cpp",
                                                               "hostlib_prove.cpp", "hostlib_pairsum.cpp",
-                                                              "hostlib_fold.cpp", "hostlib_prove_many.cpp")]
+                                                              "hostlib_fold.cpp", "hostlib_prove_many.cpp",
+                                                              "hostlib_h2g.cpp")]
     if not force and not _newer(out, srcs + _headers()):
         return out
     cxx = shutil.which("g++") or "g++"

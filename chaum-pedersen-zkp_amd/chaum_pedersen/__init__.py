@@ -131,6 +131,20 @@ class Parameters:
             raise InvalidParams("Generators g and h must be different")
         return cls(g, h)
 
+    @classmethod
+    def from_label(cls, label: bytes, gpu: Optional["Gpu"] = None) -> "Parameters":
+        """The pair derived from `label` by hashing to the group (Gpu.derive_pairs): nobody knows a
+        discrete logarithm between its g and h, nor to any other label's."""
+        return cls.from_labels([label], gpu)[0]
+
+    @classmethod
+    def from_labels(cls, labels: Sequence[bytes], gpu: Optional["Gpu"] = None) -> List["Parameters"]:
+        """One pair per label, all derived in one call (Gpu.derive_pairs)."""
+        blob, off = _message_arrays(labels, "label", _native.EACH_PAIRS_MANY_MAX,
+                                    _native.HASH_MAX_MSG - len(_native.PAIR_DST_G))
+        rows = (gpu or _gpu())._derive_pairs(len(labels), blob, off)
+        return [cls(r[:32].tobytes(), r[32:].tobytes()) for r in rows]
+
     def generator_g(self) -> bytes:
         return self.g
 
@@ -308,6 +322,67 @@ def _pair_index_tensor(pair_idx, n: int) -> None:
                             % (tuple(pair_idx.shape), n))
     if not pair_idx.is_cuda:
         raise InvalidParams("pair_idx must be a device tensor (it is on %s)" % pair_idx.device)
+
+
+def _message_arrays(msgs, what: str, max_n: int, max_len: int):
+    """The messages of Gpu.hash_to_group / the labels of Gpu.derive_pairs as (blob uint8, offsets
+    uint64[n + 1]): 1 .. max_n bytes-like items of at most max_len bytes each."""
+    if isinstance(msgs, (bytes, bytearray, memoryview, str)) or not hasattr(msgs, "__len__"):
+        raise InvalidParams("%ss must be a sequence of bytes, not %s" % (what, type(msgs).__name__))
+    n = len(msgs)
+    if n == 0:
+        raise InvalidParams("no %s given" % what)
+    if n > max_n:
+        raise InvalidParams("%d %ss, more than %d" % (n, what, max_n))
+    for i, m in enumerate(msgs):
+        if not isinstance(m, (bytes, bytearray, memoryview)):
+            raise InvalidParams("%s %d is %s, not bytes" % (what, i, type(m).__name__))
+        if len(m) > max_len:
+            raise InvalidParams("%s %d has %d bytes, more than %d" % (what, i, len(m), max_len))
+    off = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.fromiter((len(m) for m in msgs), dtype=np.uint64, count=n), out=off[1:])
+    blob = np.frombuffer(b"".join(bytes(m) for m in msgs) + b"\0", dtype=np.uint8)
+    return blob, off
+
+
+def _uniform_rows(rows) -> np.ndarray:
+    """The input of Gpu.from_uniform_bytes as uint8[n, 64], n >= 1: 64 n bytes, a uint8 array of
+    that shape, or a sequence of 64-byte strings."""
+    if isinstance(rows, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(rows), dtype=np.uint8)
+        if a.size == 0 or a.size % 64:
+            raise InvalidParams("uniform input of %d bytes is not a positive multiple of 64" % a.size)
+        a = a.reshape(-1, 64)
+    elif isinstance(rows, np.ndarray):
+        if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[1] != 64 or rows.shape[0] == 0:
+            raise InvalidParams("uniform rows must be uint8[n, 64], n >= 1, not %s%s" % (rows.dtype, rows.shape))
+        a = np.ascontiguousarray(rows)
+    else:
+        if isinstance(rows, str) or not hasattr(rows, "__len__") or len(rows) == 0:
+            raise InvalidParams("uniform rows must be a non-empty sequence of 64-byte strings")
+        for i, r in enumerate(rows):
+            if not isinstance(r, (bytes, bytearray, memoryview)) or len(r) != 64:
+                raise InvalidParams("uniform row %d is not 64 bytes" % i)
+        a = np.frombuffer(b"".join(bytes(r) for r in rows), dtype=np.uint8).reshape(-1, 64)
+    if a.shape[0] > _native.HASH_MAX_N:
+        raise InvalidParams("%d uniform rows, more than %d" % (a.shape[0], _native.HASH_MAX_N))
+    return a
+
+
+def _point_rows_tensor(t, what: str) -> int:
+    """A device form's point rows: a contiguous uint8 device tensor of 32 n bytes, n >= 1; returns n."""
+    if not hasattr(t, "data_ptr") or str(getattr(t, "dtype", None)) != "torch.uint8":
+        raise InvalidParams("%s must be a uint8 device tensor, not %s" % (what, type(t).__name__))
+    if not t.is_cuda or not t.is_contiguous():
+        raise InvalidParams("%s must be a contiguous device tensor" % what)
+    n = int(t.numel())
+    if n == 0 or n % 32:
+        raise InvalidParams("%s holds %d bytes, not a positive multiple of 32" % (what, n))
+    if n // 32 > _native.HASH_MAX_N:
+        raise InvalidParams("%s holds %d rows, more than %d" % (what, n // 32, _native.HASH_MAX_N))
+    if t.data_ptr() % 16:
+        raise InvalidParams("%s must be 16-byte aligned" % what)
+    return n // 32
 
 
 def _ptr(a) -> Optional[int]:
@@ -702,6 +777,60 @@ class Gpu:
         dp = lambda t: None if t is None else t.data_ptr()
         _native.check(self._lib.cpz_parse_proofs_device(
             self._h, n, dp(blob), dp(off), dp(r1), dp(r2), dp(s), dp(codes), dp(aux), _torch_stream(stream)))
+
+    # -- hash-to-group: sound (g, h) pairs from labels -----------------------------------------
+    def from_uniform_bytes(self, rows) -> np.ndarray:
+        """RistrettoPoint::from_uniform_bytes of n rows of 64 bytes (cpz_from_uniform_bytes):
+        uint8[n, 32] encodings."""
+        a = _uniform_rows(rows)
+        out = np.empty((a.shape[0], 32), dtype=np.uint8)
+        _native.check(self._lib.cpz_from_uniform_bytes(self._h, a.shape[0], _ptr(a), _ptr(out)))
+        return out
+
+    def hash_to_group(self, msgs: Sequence[bytes]) -> np.ndarray:
+        """from_uniform_bytes(SHA-512(m)) of every message (cpz_hash_to_group), generator_h()'s
+        construction: uint8[n, 32] encodings."""
+        blob, off = _message_arrays(msgs, "message", _native.HASH_MAX_N, _native.HASH_MAX_MSG)
+        out = np.empty((len(msgs), 32), dtype=np.uint8)
+        _native.check(self._lib.cpz_hash_to_group(self._h, len(msgs), _ptr(blob), _ptr(off), _ptr(out)))
+        return out
+
+    def _derive_pairs(self, npairs: int, blob: np.ndarray, off: np.ndarray) -> np.ndarray:
+        out = np.empty((npairs, 64), dtype=np.uint8)
+        _native.check(self._lib.cpz_derive_pairs(self._h, npairs, _ptr(blob), _ptr(off), _ptr(out)))
+        return out
+
+    def derive_pairs(self, labels: Sequence[bytes]) -> np.ndarray:
+        """One (g, h) pair per label (cpz_derive_pairs): uint8[npairs, 64] rows, g then h, with
+        g = hash_to_group(PAIR_DST_G + label) and h = hash_to_group(PAIR_DST_H + label).  At most
+        EACH_PAIRS_MANY_MAX labels of at most HASH_MAX_MSG - len(PAIR_DST_G) bytes."""
+        blob, off = _message_arrays(labels, "label", _native.EACH_PAIRS_MANY_MAX,
+                                    _native.HASH_MAX_MSG - len(_native.PAIR_DST_G))
+        return self._derive_pairs(len(labels), blob, off)
+
+    def from_uniform_bytes_device(self, uniform, points_out, stream: Optional[int] = None) -> None:
+        """Device form: uniform (uint8 tensor of 64 n bytes, any alignment) -> points_out (uint8
+        tensor of 32 n bytes, 16-byte aligned); enqueued on `stream`, not synchronised."""
+        n = _point_rows_tensor(points_out, "points_out")
+        if (not hasattr(uniform, "data_ptr") or str(uniform.dtype) != "torch.uint8" or not uniform.is_cuda
+                or not uniform.is_contiguous() or int(uniform.numel()) != 64 * n):
+            raise InvalidParams("uniform must be a contiguous uint8 device tensor of %d bytes" % (64 * n))
+        _native.check(self._lib.cpz_from_uniform_bytes_device(self._h, n, uniform.data_ptr(), points_out.data_ptr(),
+                                                              _torch_stream(stream)))
+
+    def hash_to_group_device(self, blob, off, points_out, stream: Optional[int] = None) -> None:
+        """Device form: blob (uint8 tensor, any alignment), off (int64/uint64 tensor of n + 1
+        offsets into it, trusted) -> points_out (uint8 tensor of 32 n bytes, 16-byte aligned);
+        enqueued on `stream`, not synchronised."""
+        n = _point_rows_tensor(points_out, "points_out")
+        if (not hasattr(off, "data_ptr") or str(off.dtype) not in ("torch.int64", "torch.uint64") or not off.is_cuda
+                or not off.is_contiguous() or int(off.numel()) != n + 1):
+            raise InvalidParams("off must be a contiguous int64 or uint64 device tensor of %d offsets" % (n + 1))
+        if (not hasattr(blob, "data_ptr") or str(blob.dtype) != "torch.uint8" or not blob.is_cuda
+                or not blob.is_contiguous()):
+            raise InvalidParams("blob must be a contiguous uint8 device tensor")
+        _native.check(self._lib.cpz_hash_to_group_device(self._h, n, blob.data_ptr(), off.data_ptr(),
+                                                         points_out.data_ptr(), _torch_stream(stream)))
 
     def msm(self, points: Sequence[bytes], scalars: Sequence[int]) -> bytes:
         """enc(sum [k_j] P_j) through the Pippenger kernels (cpz_msm)."""

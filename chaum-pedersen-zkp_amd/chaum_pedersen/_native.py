@@ -40,6 +40,8 @@ EXPORTED = (
     "cpz_prove_pairs", "cpz_prove_pairs_device", "cpz_ctx_load_pairs", "cpz_ctx_pairs_resident",
     "cpz_verify_batch_pairs_many", "cpz_verify_each_pairs_many",
     "cpz_prove_pairs_many", "cpz_prove_pairs_many_device",
+    "cpz_from_uniform_bytes", "cpz_from_uniform_bytes_device", "cpz_hash_to_group", "cpz_hash_to_group_device",
+    "cpz_derive_pairs",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
@@ -49,6 +51,10 @@ PAIRS_BULK_MAX_PROOFS = 1 << 20   # CPZ_PAIRS_BULK_MAX_PROOFS: proofs per cpz_ve
 EACH_PAIRS_MANY_MAX = 4096        # CPZ_EACH_PAIRS_MANY_MAX: pairs per cpz_verify_each_pairs_many call
 PROVE_PAIRS_MAX_PROOFS = 1 << 20   # CPZ_PROVE_PAIRS_MAX_PROOFS: proofs per cpz_prove_pairs / _device call
 PROVE_PAIRS_MANY_MAX = 4096       # CPZ_PROVE_PAIRS_MANY_MAX: pairs per cpz_prove_pairs_many / _device call
+HASH_MAX_MSG = 4096               # CPZ_HASH_MAX_MSG: bytes per message of cpz_hash_to_group (prefix included for cpz_derive_pairs)
+HASH_MAX_N = 1 << 20              # CPZ_HASH_MAX_N: rows per cpz_from_uniform_bytes / cpz_hash_to_group call
+PAIR_DST_G = b"chaum-pedersen-zkp-v1.0.0-generator-g/"   # CPZ_PAIR_DST_G: cpz_derive_pairs' prefix of a label for g
+PAIR_DST_H = b"chaum-pedersen-zkp-v1.0.0-generator-h/"   # CPZ_PAIR_DST_H: ... for h
 CALL_EQUATIONS_ONLY = 1   # CPZ_CALL_EQUATIONS_ONLY: commitment checks off for one call
 CALL_PARTITIONED = 2      # CPZ_CALL_PARTITIONED: cpz_verify_batch_pairs_ex searches a failing batch by blocks
 CALL_PARTITIONED_MANY = 4 # CPZ_CALL_PARTITIONED_MANY: cpz_verify_batch_pairs_many does, above PAIRS_MAX pairs
@@ -167,6 +173,16 @@ def _declare(lib):
     lib.cpz_prove_pairs_many_device.restype = ctypes.c_int
     lib.cpz_prove_pairs_many_device.argtypes = ([_p, ctypes.c_size_t, _p, ctypes.c_size_t, _p, _p, _p, _p, _p, _p] +
                                                 [_p] * 5 + [_p])
+    lib.cpz_from_uniform_bytes.restype = ctypes.c_int
+    lib.cpz_from_uniform_bytes.argtypes = [_p, ctypes.c_size_t, _p, _p]
+    lib.cpz_from_uniform_bytes_device.restype = ctypes.c_int
+    lib.cpz_from_uniform_bytes_device.argtypes = [_p, ctypes.c_size_t, _p, _p, _p]
+    lib.cpz_hash_to_group.restype = ctypes.c_int
+    lib.cpz_hash_to_group.argtypes = [_p, ctypes.c_size_t, _p, _p, _p]
+    lib.cpz_hash_to_group_device.restype = ctypes.c_int
+    lib.cpz_hash_to_group_device.argtypes = [_p, ctypes.c_size_t, _p, _p, _p, _p]
+    lib.cpz_derive_pairs.restype = ctypes.c_int
+    lib.cpz_derive_pairs.argtypes = [_p, ctypes.c_size_t, _p, _p, _p]
     lib.cpz_ctx_load_pairs.restype = ctypes.c_int
     lib.cpz_ctx_load_pairs.argtypes = [_p, ctypes.c_size_t, _p, ctypes.POINTER(ctypes.c_size_t)]
     lib.cpz_ctx_pairs_resident.restype = ctypes.c_int

@@ -315,5 +315,11 @@ hipError_t launch_decode_encode(int64_t n, const uint32_t* pts, uint8_t* ok, uin
 // cpz_verify_response: response status of s and the caller's challenge (sanitised copy to c_out).
 hipError_t launch_response_prep(int64_t n, const uint32_t* s, const uint32_t* c_in, uint32_t* c_out, uint8_t* status,
                                 int eq_only, hipStream_t st);
+// Hash-to-group (h2g.hip).  k_sha512_rows: digest[64 i ..] = SHA-512(blob[off[i] .. off[i + 1])), a
+// thread per message, every length clamped to CPZ_HASH_MAX_MSG; digest is 16-byte aligned.
+hipError_t launch_sha512_rows(int64_t n, const uint8_t* blob, const uint64_t* off, uint32_t* digest, hipStream_t st);
+// k_from_uniform: points[8 i ..] = RistrettoPoint::from_uniform_bytes(uniform[64 i ..]), encoded; a
+// lane pair per point.  points is 16-byte aligned; uniform may start at any byte.
+hipError_t launch_from_uniform(int64_t n, const uint8_t* uniform, uint32_t* points, hipStream_t st);
 
 }  // namespace cpz

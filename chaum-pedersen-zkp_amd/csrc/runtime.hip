@@ -333,6 +333,9 @@ struct cpz_ctx {
   DevBuf pt_lists, pt_offs, pt_wsum, pt_part, pt_fail, pt_tmp, pt_blocks, pt_assign;
   DevBuf pt_ldig, pt_lsum, pt_lpart, pt_lfail, pt_loc;  // the locate pass over failing blocks
   DevBuf pt_slots;  // many mode (pairs_many_part): every block's slot -> pair table
+  // hash-to-group (h2g.hip): the host forms' blob, offsets and uniform rows, the digests between
+  // the two launches, the host forms' points
+  DevBuf hg_blob, hg_off, hg_uni, hg_digest, hg_out;
   // what the last batch call's fallback did (cpz_ctx_fallback_stats)
   uint64_t fb_stats[CPZ_FALLBACK_STATS] = {};
   // commitment checks (statuses 4 and 5: the Proof::from_bytes rejections); off = equations only.
@@ -2275,6 +2278,7 @@ void cpz_ctx_destroy(cpz_ctx* ctx) {
     (void)hipStreamDestroy(ctx->copy_stream);
   }
   for (DevBuf* b : {&ctx->pz_blob, &ctx->pz_off, &ctx->pz_rows, &ctx->pz_code, &ctx->pz_aux}) b->release();
+  for (DevBuf* b : {&ctx->hg_blob, &ctx->hg_off, &ctx->hg_uni, &ctx->hg_digest, &ctx->hg_out}) b->release();
   if (ctx->span_stream) {
     (void)hipStreamSynchronize(ctx->span_stream);
     (void)hipStreamDestroy(ctx->span_stream);
@@ -4277,6 +4281,158 @@ int cpz_verify_response_ex(cpz_ctx* ctx, uint32_t flags, const uint8_t g[32], co
   if (rc) return rc;
   CPZ_HIP(hipMemcpyAsync(status_out, ctx->st.p, n, hipMemcpyDeviceToHost, ctx->stream));
   CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  return CPZ_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// Hash-to-group (h2g.hip): cpz_from_uniform_bytes, cpz_hash_to_group, cpz_derive_pairs
+// ---------------------------------------------------------------------------------------
+namespace {
+
+// The host forms' offsets, as cpz_parse_proofs takes them: non-decreasing, and no message longer
+// than CPZ_HASH_MAX_MSG less the `prefix` bytes the call puts before it.  The lowest offending
+// entry is named (`what`: "message" or "label").
+int check_hash_offsets(size_t n, const uint64_t* off, size_t prefix, const char* what) {
+  for (size_t i = 0; i < n; i++) {
+    if (off[i + 1] < off[i])
+      return fail(CPZ_EINVAL, std::string(what) + " " + std::to_string(i) + ": offsets must be non-decreasing");
+    if (off[i + 1] - off[i] > (uint64_t)CPZ_HASH_MAX_MSG - prefix)
+      return fail(CPZ_EINVAL, std::string(what) + " " + std::to_string(i) + ": " +
+                                  std::to_string(off[i + 1] - off[i] + prefix) + " bytes" +
+                                  (prefix ? " with the prefix" : "") + ", more than CPZ_HASH_MAX_MSG");
+  }
+  return CPZ_OK;
+}
+
+// n messages blob[rel[i] .. rel[i + 1]) (host memory, rel[0] == 0) -> n encodings in ctx->hg_out, on
+// ctx->stream after the context's last call; not synchronised.
+int hash_to_group_staged(cpz_ctx* ctx, size_t n, const uint8_t* blob, const uint64_t* rel) {
+  const size_t bytes = (size_t)rel[n];
+  hipStream_t st = ctx->stream;
+  if (int rc = order_after_last(ctx, st)) return rc;
+  CPZ_HIP(ctx->hg_blob.ensure(bytes + 16));
+  CPZ_HIP(ctx->hg_off.ensure((n + 1) * sizeof(uint64_t)));
+  CPZ_HIP(ctx->hg_digest.ensure(n * 64));
+  CPZ_HIP(ctx->hg_out.ensure(n * 32));
+  if (bytes) CPZ_HIP(hipMemcpyAsync(ctx->hg_blob.p, blob, bytes, hipMemcpyHostToDevice, st));
+  CPZ_HIP(hipMemcpyAsync(ctx->hg_off.p, rel, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  CPZ_HIP(cpz::launch_sha512_rows((int64_t)n, static_cast<const uint8_t*>(ctx->hg_blob.p),
+                                  static_cast<const uint64_t*>(ctx->hg_off.p), static_cast<uint32_t*>(ctx->hg_digest.p),
+                                  st));
+  CPZ_HIP(cpz::launch_from_uniform((int64_t)n, static_cast<const uint8_t*>(ctx->hg_digest.p),
+                                   static_cast<uint32_t*>(ctx->hg_out.p), st));
+  return CPZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpz_from_uniform_bytes_device(cpz_ctx* ctx, size_t n, const void* d_uniform, void* d_points_out, void* stream) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "empty input");
+  if (!d_uniform || !d_points_out) return fail(CPZ_EINVAL, "null input pointer");
+  if (n > (size_t)CPZ_HASH_MAX_N) return fail(CPZ_EINVAL, "more than CPZ_HASH_MAX_N rows");
+  if (!aligned16(d_points_out)) return fail(CPZ_EINVAL, "device point rows must be 16-byte aligned");
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (int rc = order_after_last(ctx, st)) return rc;
+  CPZ_HIP(cpz::launch_from_uniform((int64_t)n, static_cast<const uint8_t*>(d_uniform),
+                                   static_cast<uint32_t*>(d_points_out), st));
+  return record_last(ctx, st);
+}
+
+int cpz_from_uniform_bytes(cpz_ctx* ctx, size_t n, const uint8_t* uniform, uint8_t* points_out) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "empty input");
+  if (!uniform || !points_out) return fail(CPZ_EINVAL, "null input pointer");
+  if (n > (size_t)CPZ_HASH_MAX_N) return fail(CPZ_EINVAL, "more than CPZ_HASH_MAX_N rows");
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if (int rc = order_after_last(ctx, st)) return rc;
+  CPZ_HIP(ctx->hg_uni.ensure(n * 64));
+  CPZ_HIP(ctx->hg_out.ensure(n * 32));
+  CPZ_HIP(hipMemcpyAsync(ctx->hg_uni.p, uniform, n * 64, hipMemcpyHostToDevice, st));
+  CPZ_HIP(cpz::launch_from_uniform((int64_t)n, static_cast<const uint8_t*>(ctx->hg_uni.p),
+                                   static_cast<uint32_t*>(ctx->hg_out.p), st));
+  CPZ_HIP(hipMemcpyAsync(points_out, ctx->hg_out.p, n * 32, hipMemcpyDeviceToHost, st));
+  CPZ_HIP(hipStreamSynchronize(st));
+  return CPZ_OK;
+}
+
+int cpz_hash_to_group_device(cpz_ctx* ctx, size_t n, const void* d_blob, const uint64_t* d_off, void* d_points_out,
+                             void* stream) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "empty input");
+  if (!d_blob || !d_off || !d_points_out) return fail(CPZ_EINVAL, "null input pointer");
+  if (n > (size_t)CPZ_HASH_MAX_N) return fail(CPZ_EINVAL, "more than CPZ_HASH_MAX_N messages");
+  if (!aligned16(d_points_out)) return fail(CPZ_EINVAL, "device point rows must be 16-byte aligned");
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if (int rc = order_after_last(ctx, st)) return rc;
+  CPZ_HIP(ctx->hg_digest.ensure(n * 64));
+  CPZ_HIP(cpz::launch_sha512_rows((int64_t)n, static_cast<const uint8_t*>(d_blob), d_off,
+                                  static_cast<uint32_t*>(ctx->hg_digest.p), st));
+  CPZ_HIP(cpz::launch_from_uniform((int64_t)n, static_cast<const uint8_t*>(ctx->hg_digest.p),
+                                   static_cast<uint32_t*>(d_points_out), st));
+  return record_last(ctx, st);
+}
+
+int cpz_hash_to_group(cpz_ctx* ctx, size_t n, const uint8_t* blob, const uint64_t* off, uint8_t* points_out) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "empty input");
+  if (!blob || !off || !points_out) return fail(CPZ_EINVAL, "null input pointer");
+  if (n > (size_t)CPZ_HASH_MAX_N) return fail(CPZ_EINVAL, "more than CPZ_HASH_MAX_N messages");
+  if (int rc = check_hash_offsets(n, off, 0, "message")) return rc;
+  std::vector<uint64_t> rel(n + 1);
+  for (size_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  if (int rc = hash_to_group_staged(ctx, n, blob + off[0], rel.data())) return rc;
+  CPZ_HIP(hipMemcpyAsync(points_out, ctx->hg_out.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  return CPZ_OK;
+}
+
+int cpz_derive_pairs(cpz_ctx* ctx, size_t npairs, const uint8_t* labels, const uint64_t* off, uint8_t* pairs_out) {
+  static_assert(sizeof(CPZ_PAIR_DST_G) == sizeof(CPZ_PAIR_DST_H), "the two prefixes have one length");
+  constexpr size_t kPrefix = sizeof(CPZ_PAIR_DST_G) - 1;
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (npairs == 0) return fail(CPZ_EEMPTY, "empty input");
+  if (!labels || !off || !pairs_out) return fail(CPZ_EINVAL, "null input pointer");
+  if (npairs > (size_t)CPZ_EACH_PAIRS_MANY_MAX) return fail(CPZ_EINVAL, "more than CPZ_EACH_PAIRS_MANY_MAX labels");
+  if (int rc = check_hash_offsets(npairs, off, kPrefix, "label")) return rc;
+  // message 2 p = CPZ_PAIR_DST_G || label p, message 2 p + 1 = CPZ_PAIR_DST_H || label p: point rows
+  // 2 p and 2 p + 1 are then pair row p as it stands
+  const size_t n = 2 * npairs;
+  std::vector<uint64_t> rel(n + 1);
+  std::vector<uint8_t> msgs(n * kPrefix + 2 * (size_t)(off[npairs] - off[0]));
+  size_t at = 0;
+  for (size_t p = 0; p < npairs; p++) {
+    const size_t len = (size_t)(off[p + 1] - off[p]);
+    for (int k = 0; k < 2; k++) {
+      rel[2 * p + k] = at;
+      std::memcpy(msgs.data() + at, k ? CPZ_PAIR_DST_H : CPZ_PAIR_DST_G, kPrefix);
+      if (len) std::memcpy(msgs.data() + at + kPrefix, labels + off[p], len);
+      at += kPrefix + len;
+    }
+  }
+  rel[n] = at;
+  std::vector<uint8_t> rows(n * 32);
+  {
+    CallLock lock(ctx);
+    CPZ_HIP(hipSetDevice(ctx->device));
+    if (int rc = hash_to_group_staged(ctx, n, msgs.data(), rel.data())) return rc;
+    CPZ_HIP(hipMemcpyAsync(rows.data(), ctx->hg_out.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  if (int rc = check_pairs(npairs, rows.data())) return rc;  // before the caller's rows are written
+  std::memcpy(pairs_out, rows.data(), n * 32);
   return CPZ_OK;
 }
 

@@ -638,6 +638,54 @@ int cpz_parse_proofs(cpz_ctx *ctx, size_t n, const uint8_t *blob, const uint64_t
 int cpz_parse_proofs_device(cpz_ctx *ctx, size_t n, const void *d_blob, const uint64_t *d_off, void *d_r1,
                             void *d_r2, void *d_s, void *d_code, void *d_aux, void *stream);
 
+/* Hash-to-group on the device: sound (g, h) pairs from labels.  generator_h() of the reference is
+ * RistrettoPoint::from_uniform_bytes(SHA-512(dst)) (ristretto.rs:27, 86-91); these calls run that
+ * construction -- FIPS 180-4 SHA-512, then the ristretto255 one-way map of RFC 9496 4.3.4 -- for n
+ * messages at once, so that nobody knows a discrete logarithm between any two of the points.
+ *   cpz_from_uniform_bytes  n rows of 64 uniform bytes -> n 32-byte encodings.  Bit 255 of each
+ *                           32-byte half is ignored and a half in [p, 2^255) stands for its
+ *                           residue, as dalek's FieldElement::from_bytes takes it.
+ *   cpz_hash_to_group       points_out[i] = from_uniform_bytes(SHA-512(blob[off[i] .. off[i+1]))).
+ *                           The message "chaum-pedersen-zkp-v1.0.0-generator-h" gives the h of
+ *                           cpz_default_generators.
+ *   cpz_derive_pairs        pairs_out row p (64 bytes, g then h) =
+ *                           ( hash_to_group(CPZ_PAIR_DST_G || label_p),
+ *                             hash_to_group(CPZ_PAIR_DST_H || label_p) ),
+ *                           label_p = labels[off[p] .. off[p+1]); the rows go as they are into
+ *                           every `pairs` argument of this header.  At most
+ *                           CPZ_EACH_PAIRS_MANY_MAX labels; the 2 npairs prefixed messages are
+ *                           built on the host and take one hash launch and one map launch.  Both
+ *                           prefixes have one length and end in '/', so distinct labels give
+ *                           distinct messages and the empty label does not give the default h.
+ *                           The rows are then checked as every call checks its pairs: a row with
+ *                           the identity or with g == h is CPZ_EGENERATOR naming the pair (no
+ *                           label is known to reach this) and nothing is written.
+ * Host forms: offsets as for cpz_parse_proofs (n + 1 of them, relative to off[0], non-decreasing).
+ * n == 0 is CPZ_EEMPTY; a null pointer, n > CPZ_HASH_MAX_N (CPZ_EACH_PAIRS_MANY_MAX labels),
+ * decreasing offsets or a message longer than CPZ_HASH_MAX_MSG bytes -- for cpz_derive_pairs the
+ * label plus the prefix -- is CPZ_EINVAL, cpz_last_error naming the lowest offending entry.  Every
+ * check is made before anything is launched or written; the calls return synchronised.
+ * Device forms: enqueued on `stream` (NULL: the context's own) after the context's last call, not
+ * synchronised, like cpz_verify_each_device.  d_points_out must be 16-byte aligned; the blob and
+ * the uniform rows may start at any byte.  The offsets are trusted, except that every length is
+ * clamped to CPZ_HASH_MAX_MSG in the kernel.
+ * The calls record no stage and leave cpz_ctx_fallback_stats alone.
+ * Measured (profiles/hash_to_group_ab.json, tools/hash_to_group_ab.py; host clocks around the
+ * synchronous calls, medians): cpz_derive_pairs of 64 / 1000 / 4096 labels 0.20 / 0.35 / 0.80 ms,
+ * cpz_hash_to_group of 2^16 short messages through the Python wrapper 8.3 ms.  The other side there is
+ * the Python oracle's map, timed in the same run on 64 points (0.21 ms a point) and scaled, not run:
+ * 27 / 420 / 1722 ms and 13.8 s. */
+#define CPZ_HASH_MAX_MSG 4096 /* bytes per message */
+#define CPZ_HASH_MAX_N 1048576 /* 1 << 20 */
+#define CPZ_PAIR_DST_G "chaum-pedersen-zkp-v1.0.0-generator-g/"
+#define CPZ_PAIR_DST_H "chaum-pedersen-zkp-v1.0.0-generator-h/"
+int cpz_from_uniform_bytes(cpz_ctx *ctx, size_t n, const uint8_t *uniform, uint8_t *points_out);
+int cpz_from_uniform_bytes_device(cpz_ctx *ctx, size_t n, const void *d_uniform, void *d_points_out, void *stream);
+int cpz_hash_to_group(cpz_ctx *ctx, size_t n, const uint8_t *blob, const uint64_t *off, uint8_t *points_out);
+int cpz_hash_to_group_device(cpz_ctx *ctx, size_t n, const void *d_blob, const uint64_t *d_off,
+                             void *d_points_out, void *stream);
+int cpz_derive_pairs(cpz_ctx *ctx, size_t npairs, const uint8_t *labels, const uint64_t *off, uint8_t *pairs_out);
+
 /* Single-process multi-GPU forms: one context per GPU (e.g. the 8 GPUs of a node, or
  * several contexts on one GPU), the n proofs cut into nctx contiguous shards whose
  * boundaries are multiples of 256 proofs (the RLC weight-block granule), each shard

@@ -86,10 +86,16 @@ inline Result status_result(uint8_t st) {
   }
 }
 
+class Device;
+
 struct Parameters {  // gadgets.rs:25-118
   Bytes32 g, h;
   Parameters() { cpz_default_generators(g.data(), h.data()); }
   Parameters(const Bytes32& g_, const Bytes32& h_) : g(g_), h(h_) {}
+  // The pair derived from a label by hashing to the group (cpz_derive_pairs): g and h are
+  // from_uniform_bytes(SHA-512(CPZ_PAIR_DST_G / CPZ_PAIR_DST_H || label)), generator_h()'s
+  // construction (ristretto.rs:86-91), so nobody knows a discrete logarithm between them.
+  static Result from_label(Device& dev, const uint8_t* label, std::size_t len, Parameters* out);
 };
 
 struct Statement {  // gadgets.rs:177-239
@@ -157,6 +163,20 @@ class Device {
   cpz_ctx* ctx_ = nullptr;
   int rc_ = CPZ_EINVAL;
 };
+
+inline Result Parameters::from_label(Device& dev, const uint8_t* label, std::size_t len, Parameters* out) {
+  const uint64_t off[2] = {0, len};
+  const uint8_t pad = 0;
+  uint8_t row[64];
+  const int rc = cpz_derive_pairs(dev.get(), 1, len ? label : &pad, off, row);
+  if (rc == CPZ_EINVAL || rc == CPZ_EGENERATOR) return Result::err(ErrorKind::InvalidParams, cpz_last_error());
+  if (rc != CPZ_OK) return Result::err(ErrorKind::Device, cpz_last_error());
+  if (out) {
+    std::memcpy(out->g.data(), row, 32);
+    std::memcpy(out->h.data(), row + 32, 32);
+  }
+  return Result::ok();
+}
 
 // Statement::validate (gadgets.rs:234-238 -> ristretto.rs:173-185): y1 and y2 must be group
 // elements, i.e. their encodings must decode (on the device).

@@ -12,7 +12,7 @@ use std::env;
 use std::path::PathBuf;
 use std::process::Command;
 
-const UNITS: [&str; 5] = ["kernels.hip", "wide.hip", "rlc.hip", "part.hip", "runtime.hip"];
+const UNITS: [&str; 6] = ["kernels.hip", "wide.hip", "rlc.hip", "part.hip", "h2g.hip", "runtime.hip"];
 
 fn main() {
     println!("cargo:rerun-if-env-changed=CPZ_LIB_DIR");

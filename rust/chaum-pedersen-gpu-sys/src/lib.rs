@@ -59,6 +59,10 @@ pub const CPZ_PAIRS_BULK_MAX_PROOFS: usize = 1048576;
 pub const CPZ_EACH_PAIRS_MANY_MAX: usize = 4096;
 pub const CPZ_PROVE_PAIRS_MAX_PROOFS: usize = 1048576;
 pub const CPZ_PROVE_PAIRS_MANY_MAX: usize = 4096;
+pub const CPZ_HASH_MAX_MSG: usize = 4096;
+pub const CPZ_HASH_MAX_N: usize = 1048576;
+pub const CPZ_PAIR_DST_G: &[u8] = b"chaum-pedersen-zkp-v1.0.0-generator-g/";
+pub const CPZ_PAIR_DST_H: &[u8] = b"chaum-pedersen-zkp-v1.0.0-generator-h/";
 pub const CPZ_FALLBACK_STATS: usize = 8;
 pub const CPZ_FALLBACK_NONE: u64 = 0;
 pub const CPZ_FALLBACK_BISECTION: u64 = 1;
@@ -203,6 +207,15 @@ extern "C" {
     pub fn cpz_parse_proofs_device(ctx: *mut cpz_ctx, n: usize, d_blob: *const c_void, d_off: *const u64,
                                    d_r1: *mut c_void, d_r2: *mut c_void, d_s: *mut c_void, d_code: *mut c_void,
                                    d_aux: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn cpz_from_uniform_bytes(ctx: *mut cpz_ctx, n: usize, uniform: *const u8, points_out: *mut u8) -> c_int;
+    pub fn cpz_from_uniform_bytes_device(ctx: *mut cpz_ctx, n: usize, d_uniform: *const c_void,
+                                         d_points_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn cpz_hash_to_group(ctx: *mut cpz_ctx, n: usize, blob: *const u8, off: *const u64,
+                             points_out: *mut u8) -> c_int;
+    pub fn cpz_hash_to_group_device(ctx: *mut cpz_ctx, n: usize, d_blob: *const c_void, d_off: *const u64,
+                                    d_points_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn cpz_derive_pairs(ctx: *mut cpz_ctx, npairs: usize, labels: *const u8, off: *const u64,
+                            pairs_out: *mut u8) -> c_int;
     pub fn cpz_verify_each_multi(ctxs: *const *mut cpz_ctx, nctx: c_int, g: *const u8, h: *const u8, n: usize,
                                  y1: *const u8, y2: *const u8, r1: *const u8, r2: *const u8, s: *const u8,
                                  ctx_bytes: *const u8, ctx_off: *const u64, ctx_present: *const u8,
