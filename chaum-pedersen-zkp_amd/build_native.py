@@ -141,7 +141,7 @@ def build_hosttest(force: bool = False, out: str = HOSTTEST, defines=()) -> str:
     srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("hostlib.cpp", "hostlib_joint.cpp", "hostlib_lean.cpp",
                                                               "hostlib_prove.cpp", "hostlib_pairsum.cpp",
                                                               "hostlib_fold.cpp", "hostlib_prove_many.cpp",
-                                                              "hostlib_h2g.cpp")]
+                                                              "hostlib_h2g.cpp", "hostlib_gh.cpp")]
     if not force and not _newer(out, srcs + _headers()):
         return out
     cxx = shutil.which("g++") or "g++"

@@ -26,14 +26,14 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _native
-from ._native import (CpzError, STATUS_BAD_POINT, STATUS_BAD_SCALAR, STATUS_EQ_FAIL,
+from ._native import (CpzError, STATUS_BAD_GENERATOR, STATUS_BAD_POINT, STATUS_BAD_SCALAR, STATUS_EQ_FAIL,
                       STATUS_IDENTITY, STATUS_OK, STATUS_ZERO_S)
 
 __all__ = [
     "Error", "InvalidParams", "InvalidScalar", "InvalidGroupElement", "CpzError",
     "Parameters", "Statement", "Proof", "BatchVerifier", "Gpu", "VerifyResult", "Transcript", "Verifier", "Prover",
     "MAX_BATCH_SIZE", "RLC_MIN_GROUP", "PROTOCOL_VERSION", "STATUS_OK", "STATUS_EQ_FAIL", "STATUS_BAD_POINT",
-    "STATUS_BAD_SCALAR", "STATUS_IDENTITY", "STATUS_ZERO_S", "default_generators", "verify_each_multi", "verify_batch_multi",
+    "STATUS_BAD_SCALAR", "STATUS_IDENTITY", "STATUS_ZERO_S", "STATUS_BAD_GENERATOR", "default_generators", "verify_each_multi", "verify_batch_multi",
 ]
 
 MAX_BATCH_SIZE = 1000          # batch.rs:48
@@ -87,6 +87,8 @@ class VerifyResult:
     def error(self) -> Optional[Error]:
         if self.status == STATUS_OK:
             return None
+        if self.status == STATUS_BAD_GENERATOR:  # verify_each_gh: Parameters::with_generators fails for the entry
+            return InvalidParams("Invalid generators")
         cls, msg = _STATUS_ERR[self.status]
         return cls(msg)
 
@@ -284,6 +286,46 @@ def _ctx_arrays(contexts: Optional[Sequence[Optional[bytes]]], n: int):
     np.cumsum(lens, out=off[1:])
     blob = np.frombuffer(b"".join(c for c in contexts if c is not None) or b"\0", dtype=np.uint8).copy()
     return blob, off, present
+
+
+def _gh_rows(n: int, named) -> List[np.ndarray]:
+    """The rows of Gpu.verify_each_gh / challenges_gh as uint8[n, 32] arrays: every one holds exactly
+    n rows of 32 bytes, 1 <= n <= PAIRS_BULK_MAX_PROOFS, checked here before the library is called."""
+    if n < 1:
+        raise InvalidParams("Cannot verify empty batch")
+    if n > _native.PAIRS_BULK_MAX_PROOFS:
+        raise InvalidParams("%d entries, more than %d" % (n, _native.PAIRS_BULK_MAX_PROOFS))
+    out = []
+    for a, name in named:
+        try:
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.uint8))
+        except (TypeError, ValueError):
+            raise InvalidParams("%s must be rows of 32 bytes" % name)
+        if a.shape != (n, 32):
+            raise InvalidParams("%s must hold %d rows of 32 bytes, not shape %s" % (name, n, a.shape))
+        out.append(a)
+    return out
+
+
+def _gh_row_tensors(named) -> int:
+    """The rows of Gpu.verify_each_gh_device: contiguous uint8 device tensors of n x 32 bytes each, the
+    same n for all, 1 <= n <= PAIRS_BULK_MAX_PROOFS; returns n.  (Alignment is the library's check.)"""
+    n = None
+    for t, name in named:
+        if not hasattr(t, "data_ptr") or str(getattr(t, "dtype", None)) != "torch.uint8":
+            raise InvalidParams("%s must be a uint8 device tensor, not %s" % (name, type(t).__name__))
+        if not t.is_cuda or not t.is_contiguous():
+            raise InvalidParams("%s must be a contiguous device tensor" % name)
+        m = int(t.numel())
+        if m == 0 or m % 32:
+            raise InvalidParams("%s holds %d bytes, not a positive multiple of 32" % (name, m))
+        if n is None:
+            n = m // 32
+        if m != 32 * n:
+            raise InvalidParams("%s holds %d rows, not %d" % (name, m // 32, n))
+    if n > _native.PAIRS_BULK_MAX_PROOFS:
+        raise InvalidParams("%d entries, more than %d" % (n, _native.PAIRS_BULK_MAX_PROOFS))
+    return n
 
 
 def _pair_indices(pair_idx, n: int, npairs: int) -> np.ndarray:
@@ -545,6 +587,35 @@ class Gpu:
         _native.check(self._lib.cpz_verify_each_pairs_many(
             self._h, _flags(equations_only), npairs, _ptr(gh), n, _ptr(idx), *[_ptr(a) for a in arrs], _ptr(blob),
             _ptr(off), _ptr(present), _ptr(out)))
+        return out
+
+    def verify_each_gh(self, g, h, y1, y2, r1, r2, s, contexts=None, equations_only: bool = False) -> np.ndarray:
+        """Status per proof (uint8[n]) where entry i carries its own generators, rows g[i] and h[i]
+        (cpz_verify_each_gh): decryption-share and VRF / OPRF evaluation proofs, where h is a fresh
+        point per proof.  STATUS_BAD_GENERATOR where Parameters.with_generators(g[i], h[i]) would
+        fail (a generator does not decode or is the identity, or g[i] == h[i]) -- it wins over every
+        other status and is never an exception; otherwise what verify_each returns for the entry
+        under (g[i], h[i]).  Any number of distinct pairs, up to PAIRS_BULK_MAX_PROOFS entries;
+        nothing is built per pair and no cached set is touched.  Shapes and lengths are checked
+        here before the library is called."""
+        n = len(y1)
+        arrs = _gh_rows(n, ((g, "g"), (h, "h"), (y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2"), (s, "s")))
+        blob, off, present = _ctx_arrays(contexts, n)
+        out = np.empty(n, dtype=np.uint8)
+        _native.check(self._lib.cpz_verify_each_gh(
+            self._h, _flags(equations_only), n, *[_ptr(a) for a in arrs], _ptr(blob), _ptr(off), _ptr(present),
+            _ptr(out)))
+        return out
+
+    def challenges_gh(self, g, h, y1, y2, r1, r2, contexts=None) -> np.ndarray:
+        """The Fiat-Shamir challenges ((n, 32) scalars) of entries that carry their own generators
+        (cpz_challenges_gh): entry i's is what challenges returns for it under (g[i], h[i])."""
+        n = len(y1)
+        arrs = _gh_rows(n, ((g, "g"), (h, "h"), (y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2")))
+        blob, off, present = _ctx_arrays(contexts, n)
+        out = np.empty((n, 32), dtype=np.uint8)
+        _native.check(self._lib.cpz_challenges_gh(
+            self._h, n, *[_ptr(a) for a in arrs], _ptr(blob), _ptr(off), _ptr(present), _ptr(out)))
         return out
 
     def challenges(self, y1, y2, r1, r2, contexts=None, params: Optional[Parameters] = None) -> np.ndarray:
@@ -886,6 +957,21 @@ class Gpu:
         _native.check(self._lib.cpz_verify_each_pairs_device(
             self._h, _flags(equations_only), npairs, _ptr(gh), n, dp(pair_idx), dp(y1), dp(y2), dp(r1), dp(r2), dp(s),
             dp(ctx_bytes), dp(ctx_off), dp(ctx_present), dp(status_out), _torch_stream(stream)))
+
+    def verify_each_gh_device(self, g, h, y1, y2, r1, r2, s, status_out, stream: Optional[int] = None, ctx_bytes=None,
+                              ctx_off=None, ctx_present=None, equations_only: bool = False) -> None:
+        """verify_each_gh on device tensors (cpz_verify_each_gh_device): the seven rows uint8 (n, 32),
+        16-B aligned (hash_to_group_device's output serves as h), status_out a uint8 tensor of n.
+        Enqueued on `stream` and NOT synchronised: read status_out after the stream's own
+        synchronisation.  Nothing is copied to or from the host."""
+        n = _gh_row_tensors(((g, "g"), (h, "h"), (y1, "y1"), (y2, "y2"), (r1, "r1"), (r2, "r2"), (s, "s")))
+        if (not hasattr(status_out, "data_ptr") or str(getattr(status_out, "dtype", None)) != "torch.uint8"
+                or not status_out.is_cuda or not status_out.is_contiguous() or int(status_out.numel()) != n):
+            raise InvalidParams("status_out must be a contiguous uint8 device tensor of %d elements" % n)
+        dp = lambda t: None if t is None else t.data_ptr()
+        _native.check(self._lib.cpz_verify_each_gh_device(
+            self._h, _flags(equations_only), n, dp(g), dp(h), dp(y1), dp(y2), dp(r1), dp(r2), dp(s), dp(ctx_bytes),
+            dp(ctx_off), dp(ctx_present), dp(status_out), _torch_stream(stream)))
 
     def verify_response_device(self, y1, y2, r1, r2, s, c, status_out, params: Optional[Parameters] = None,
                                stream: Optional[int] = None) -> None:

@@ -25,6 +25,7 @@ STATUS_BAD_POINT = 2
 STATUS_BAD_SCALAR = 3
 STATUS_IDENTITY = 4
 STATUS_ZERO_S = 5
+STATUS_BAD_GENERATOR = 6   # cpz_verify_each_gh only: the entry's own (g, h) is no valid pair
 
 EXPORTED = (
     "cpz_device_count", "cpz_ctx_create", "cpz_ctx_destroy", "cpz_last_error",
@@ -42,6 +43,7 @@ EXPORTED = (
     "cpz_prove_pairs_many", "cpz_prove_pairs_many_device",
     "cpz_from_uniform_bytes", "cpz_from_uniform_bytes_device", "cpz_hash_to_group", "cpz_hash_to_group_device",
     "cpz_derive_pairs",
+    "cpz_verify_each_gh", "cpz_verify_each_gh_device", "cpz_challenges_gh",
 )
 PAIRS_MAX = 64            # CPZ_PAIRS_MAX: pairs per cpz_verify_each_pairs call
 PAIRS_MAX_PROOFS = 2048   # CPZ_PAIRS_MAX_PROOFS: proofs per such call
@@ -107,6 +109,13 @@ def _declare(lib):
     lib.cpz_verify_each_pairs_many.restype = ctypes.c_int
     lib.cpz_verify_each_pairs_many.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] +
                                                [_p] * 5 + [_p, _p, _p, _p])
+    lib.cpz_verify_each_gh.restype = ctypes.c_int
+    lib.cpz_verify_each_gh.argtypes = [_p, ctypes.c_uint32, ctypes.c_size_t, _p, _p] + [_p] * 5 + [_p, _p, _p, _p]
+    lib.cpz_verify_each_gh_device.restype = ctypes.c_int
+    lib.cpz_verify_each_gh_device.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, _p] + [_p] * 5 +
+                                              [_p, _p, _p, _p, _p])
+    lib.cpz_challenges_gh.restype = ctypes.c_int
+    lib.cpz_challenges_gh.argtypes = [_p, ctypes.c_size_t, _p, _p] + [_p] * 4 + [_p, _p, _p, _p]
     lib.cpz_verify_each_pairs_device.restype = ctypes.c_int
     lib.cpz_verify_each_pairs_device.argtypes = ([_p, ctypes.c_uint32, ctypes.c_size_t, _p, ctypes.c_size_t, _p] +
                                                  [_p] * 5 + [_p, _p, _p, _p, _p])

@@ -296,6 +296,30 @@ hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hip
 // desc[p] into micro[p * kPairMicroInts ..]: a quad per (pair, generator).  A generator that does
 // not decode leaves identity tables (launch_pair_desc's flags are what rejects such a pair).
 hipError_t launch_pair_micro(const PairDesc* desc, int npairs, int32_t* micro, hipStream_t st);
+// cpz_verify_each_gh: entry i verifies under its own generators, rows g / h (each_gh.h).  One block
+// for the two kernels of a chunk: k_challenge_gh writes c and the response statuses, and
+// k_verify_quad_gh reads them and leaves the final statuses.
+struct GhArgs {
+  int64_t n;
+  const uint32_t* g;             // n x 8 words each (SoA rows of 32 bytes)
+  const uint32_t* h;
+  const uint32_t* y1;
+  const uint32_t* y2;
+  const uint32_t* r1;
+  const uint32_t* r2;
+  const uint32_t* s;             // may be null (k_challenge_gh: no response statuses)
+  const uint8_t* ctx_bytes;      // concatenated contexts
+  const uint64_t* ctx_off;       // n + 1 offsets, or null: no contexts
+  const uint8_t* ctx_present;    // n flags (Some/None), or null: all Some when ctx_off set
+  uint32_t* c;                   // n x 8 words: the challenges
+  uint8_t* status;               // n
+  char* scratch = nullptr;       // k_verify_quad_gh: kGhProofScratch bytes of tables per proof
+  int64_t max_proofs = 0;        // the proofs scratch holds (the runtime: half of verify_quad_max)
+  int eq_only = 0;               // commitment checks off (response_status, the identity-commitment status)
+  StrobeSnap s0;                 // the sponge after Transcript::new(): no pair enters it
+};
+hipError_t launch_challenge_gh(const GhArgs& a, hipStream_t st);
+hipError_t launch_verify_quad_gh(const GhArgs& a, hipStream_t st);
 // Device-resident indices of a mixed-pair call against npairs: *first (set to kPairIdxOk by the
 // caller, on the same stream) ends as the lowest i with idx[i] >= npairs, or stays kPairIdxOk.
 constexpr uint32_t kPairIdxOk = 0xffffffffu;

@@ -23,6 +23,10 @@
 //                        mixed additions from the
 //                        fixed-base comb of B in HBM (radix-2^16 digits).
 //                        batch.rs:185-231, verifier/mod.rs:144-171
+//   k_challenge_gh       1 thread / proof: the challenge of an entry that carries its own (g, h) rows
+//                        (cpz_verify_each_gh), always on the LDS sponge image
+//   k_verify_quad_gh     eight lanes per proof, the proof's generators decoded and their small
+//                        tables built in the proof's own quads (each_gh.h)
 //   k_parse_proofs       bulk Proof::from_bytes (gadgets.rs:364-489) into SoA rows + codes
 //   k_prove_points /     synthetic-input generator: Prover::prove_with_transcript
 //   k_prove_response     (prover/mod.rs:86-131) with ChaCha20-derived witnesses/nonces
@@ -46,6 +50,7 @@
 #include "fe16.h"
 #include "keccak_wave.h"
 #include "proof_digits.h"
+#include "each_gh.h"
 
 namespace cpz {
 
@@ -265,6 +270,48 @@ __global__ void __launch_bounds__(kChallengeBlock) k_challenge_pairs(ChallengeAr
   __shared__ uint32_t lds[50 * kChallengeBlock];
   challenge_body<true>(a, pa, lds);
 }
+// cpz_verify_each_gh: entry i carries its own generators, rows a.g / a.h.  The transcript prefix
+// differs from entry to entry, so no fixed schedule applies: every entry takes challenge_generic's
+// path, the byte-wise STROBE code on the thread's image of the sponge in LDS, from the one snapshot
+// no pair enters (a.s0, after Transcript::new()).  Response statuses as k_challenge_pairs writes them.
+__global__ void __launch_bounds__(kChallengeBlock) k_challenge_gh(GhArgs a) {
+  __shared__ uint32_t lds[50 * kChallengeBlock];
+  const int64_t i = (int64_t)blockIdx.x * kChallengeBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const bool has_ctx = a.ctx_off != nullptr && (a.ctx_present == nullptr || a.ctx_present[i] != 0);
+  uint32_t g[8], h[8], y1[8], y2[8], r1[8], r2[8];
+  load_words8(g, a.g, i);
+  load_words8(h, a.h, i);
+  load_words8(y1, a.y1, i);
+  load_words8(y2, a.y2, i);
+  load_words8(r1, a.r1, i);
+  load_words8(r2, a.r2, i);
+  const uint64_t b0 = has_ctx ? a.ctx_off[i] : 0;
+  const uint64_t b1 = has_ctx ? a.ctx_off[i + 1] : 0;
+  LdsState st{lds, (int)threadIdx.x, kChallengeBlock};
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(a.s0.state);
+#pragma unroll
+    for (int w = 0; w < 50; w++) lds[w * kChallengeBlock + threadIdx.x] = src[w];
+  }
+  Strobe<LdsState> s(st, a.s0.pos, a.s0.pos_begin, (uint8_t)a.s0.flags);
+  const sc c = challenge_gh(s, has_ctx, a.ctx_bytes + b0, (uint32_t)(b1 - b0), g, h, y1, y2, r1, r2);
+  store_words8(a.c, i, c.w);
+  if (a.s != nullptr) {
+    uint32_t w[8];
+    load_words8(w, a.s, i);
+    a.status[i] = response_status(w, a.eq_only != 0);
+  }
+}
+
+hipError_t launch_challenge_gh(const GhArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (!a.g || !a.h || !a.c) return hipErrorInvalidValue;
+  const int64_t blocks = (a.n + kChallengeBlock - 1) / kChallengeBlock;
+  hipLaunchKernelGGL(k_challenge_gh, dim3((unsigned)blocks), dim3(kChallengeBlock), 0, st, a);
+  return hipGetLastError();
+}
+
 // No-context fast path (verify.h, challenge_fixed): the sponge in 50 registers, the
 // framing as two constant masks, two permutations, no LDS.  Chosen by the runtime when the
 // prefix snapshot sits at the fixed position.
@@ -1348,6 +1395,142 @@ hipError_t launch_verify_quad_pairs(const VerifyArgs& a, const PairArgs& pa, hip
     return hipGetLastError();
   }
   hipLaunchKernelGGL((k_verify_quad<false, true, true>), dim3((unsigned)((slots + 31) / 32)), dim3(256), 0, st, a, pa);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// cpz_verify_each_gh: the eight-lane kernel for entries that carry their own generators (rows
+// a.g / a.h), a sibling of k_verify_quad so that every instantiation of that kernel keeps its
+// code.  The pair is used once, so what k_pair_micro builds per pair is built here per proof, in
+// the proof's own quads: lane 0 of quad e decodes Y, lane 1 R and lane 2 -- idle in k_verify_quad
+// -- B (g for e = 0, h for e = 1), the three decodes side by side.  B is broadcast, quad_table of B
+// written, B doubled 128 times (p3_dbl_n_quad) and quad_table of 2^128 B written; then the tables
+// of -Y and -+R, so that only the lanes' own decoded point stays live across the chain.  The four
+// tables lie in the launch's scratch (each_gh.h gh_quad_tab: kGhProofScratch bytes per proof,
+// twice k_verify_quad's).  The Straus loop is the kMicro arm's: radix-16 digits of s' and
+// pair_micro_window per window, against the quad's own tables of B and 2^128 B.
+// The generator verdict (each_gh.h gh_generators_bad: a generator does not decode, is the
+// identity, or g == h) comes from lane 2's decode flags and the row words and wins over every
+// other status; such an entry's lanes run the same code to the end (a failed decode leaves field
+// elements that are no point, which the arithmetic takes like any other), so no lane leaves its
+// quad before the last cross-lane step.
+// ---------------------------------------------------------------------------------------
+static_assert(kGhTableInts == kPairMicroTableInts, "pair_micro_window finds the table of 2^128 B after that of B");
+static_assert(kGhProofScratch == 2 * kQuadProofScratch, "a proof takes twice the eight-lane kernel's scratch");
+
+template <int K>
+__device__ __forceinline__ ge_p3 p3_bcast_lane(const ge_p3& P) {
+  ge_p3 r;
+  r.X = fe_quad_bcast<K>(P.X); r.Y = fe_quad_bcast<K>(P.Y); r.Z = fe_quad_bcast<K>(P.Z); r.T = fe_quad_bcast<K>(P.T);
+  return r;
+}
+
+__global__ void __launch_bounds__(256) k_verify_quad_gh(GhArgs a) {
+  const int t = threadIdx.x;
+  const int64_t i = (int64_t)blockIdx.x * 32 + (t >> 3);
+  const int e = (t >> 2) & 1, q = t & 3;
+  if (i >= a.n) return;  // a proof's eight lanes together
+  int32_t* tab = reinterpret_cast<int32_t*>(a.scratch) + gh_quad_tab((int64_t)blockIdx.x * 64 + (t >> 2));  // by slot
+  uint32_t ud[4], vd[4], sd[8];
+  bool vneg;
+  const uint8_t st_s = a.status[i];
+  {
+    uint32_t sw[8], cw[8];
+    load_words8(sw, a.s, i);
+    load_words8(cw, a.c, i);
+    // challenge split and digits, identical on every lane (k_verify_quad's kMicro arm)
+    uint32_t u[4], va[4];
+    sc_half_split(cw, u, va, vneg);
+    sc_recode_radix16_half(ud, u);
+    sc_recode_radix16_half(vd, va);
+    sc vs, ss;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      vs.w[k] = k < 4 ? va[k] : 0u;
+      ss.w[k] = sw[k];
+    }
+    sc sp = sc_mul(vs, ss);
+    if (vneg) sp = sc_neg(sp);
+    sc_recode_radix16(sd, sp.w);  // digits 0..31 on B, digits 32..63 on 2^128 B
+  }
+  // lane 0 decodes this equation's Y, lane 1 its R, lane 2 its generator
+  ge_p3 P = ge_identity();
+  bool ok = true;
+  if (q < 3) {
+    uint32_t enc[8];
+    load_words8(enc, q == 0 ? (e ? a.y2 : a.y1) : (q == 1 ? (e ? a.r2 : a.r1) : (e ? a.h : a.g)), i);
+    ok = ristretto_decode(P, enc);
+  }
+  {
+    ge_p3 B = p3_bcast_lane<2>(P);
+    quad_table(tab + kGhTabB * kGhTableInts, B, q);
+    B = p3_dbl_n_quad(B, 128, q);
+    quad_table(tab + kGhTabB2 * kGhTableInts, B, q);
+  }
+  quad_table(tab + kGhTabY * kGhTableInts, ge_neg(p3_bcast_lane<0>(P)), q);
+  {
+    ge_p3 R = p3_bcast_lane<1>(P);
+    if (!vneg) R = ge_neg(R);
+    quad_table(tab + kGhTabR * kGhTableInts, R, q);
+  }
+  __threadfence_block();  // the quad's other lanes' fields (a negative digit reads them)
+  // Q = [u] Y' + [|v|] R' + [s'] B: identity (mod E[4]) iff the equation holds
+  const int32_t* mt = tab + kGhTabB * kGhTableInts;
+  ge_p3 acc = ge_identity();
+#pragma unroll 1
+  for (int j = 0; j < 4; j++) {
+    const uint32_t wu = ud[3], wv = vd[3], wg = sd[3], wg2 = sd[7];
+#pragma unroll
+    for (int k = 3; k > 0; k--) {
+      ud[k] = ud[k - 1];
+      vd[k] = vd[k - 1];
+      sd[k] = sd[k - 1];
+      sd[4 + k] = sd[4 + k - 1];
+    }
+#pragma unroll 1
+    for (int m = 7; m >= 0; m--) {
+      const int du = ((int32_t)(wu << (28 - 4 * m))) >> 28;
+      const int dv = ((int32_t)(wv << (28 - 4 * m))) >> 28;
+      const int dg = ((int32_t)(wg << (28 - 4 * m))) >> 28;  // digit 8 (3 - j) + m of s' (and of s' >> 128)
+      const int dg2 = ((int32_t)(wg2 << (28 - 4 * m))) >> 28;
+      const fe ey = quad_lookup(tab + kGhTabY * kGhTableInts, du, q), er = quad_lookup(tab + kGhTabR * kGhTableInts, dv, q);
+      if (j != 0 || m != 7) acc = p3_dbl_n_quad(acc, 4, q);
+      acc = ge_add_quad(acc, cached_of_field(ey), q);
+      acc = ge_add_quad(acc, cached_of_field(er), q);
+      acc = pair_micro_window(acc, mt, dg, dg2, q);
+    }
+  }
+  // the proof's verdict from its two quads (lane 0 of quad e = 0 writes it)
+  int eq = ristretto_is_identity(acc) ? 1 : 0;
+  eq &= __shfl_xor(eq, 4);
+  int bad = ok ? 0 : (q == 2 ? 2 : 1);  // bit 0: Y or R, bit 1: a generator did not decode
+  bad |= __shfl_xor(bad, 1);
+  bad |= __shfl_xor(bad, 2);
+  bad |= __shfl_xor(bad, 4);
+  if ((t & 7) != 0) return;
+  uint32_t w1[8], w2[8];
+  load_words8(w1, a.g, i);
+  load_words8(w2, a.h, i);
+  const bool gbad = gh_generators_bad((bad & 2) == 0, w1, w2);
+  load_words8(w1, a.r1, i);
+  load_words8(w2, a.r2, i);
+  const bool rid = words8_zero(w1) || words8_zero(w2);
+  uint8_t st;
+  if (gbad) st = kStBadGenerator;
+  else if (bad & 1) st = kStBadPoint;
+  else if (st_s == kStBadScalar) st = kStBadScalar;
+  else if (rid && !a.eq_only) st = kStIdentity;
+  else if (st_s == kStZeroS) st = kStZeroS;
+  else st = eq ? kStOk : kStEqFail;
+  a.status[i] = st;
+}
+
+// a.c / a.status from launch_challenge_gh; at most a.max_proofs proofs, the proofs whose tables
+// a.scratch holds (kGhProofScratch bytes each).
+hipError_t launch_verify_quad_gh(const GhArgs& a, hipStream_t st) {
+  if (a.n <= 0) return hipSuccess;
+  if (!a.g || !a.h || !a.c || !a.status || !a.scratch || a.n > a.max_proofs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_verify_quad_gh, dim3((unsigned)((a.n + 31) / 32)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

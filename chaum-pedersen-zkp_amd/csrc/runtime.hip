@@ -21,6 +21,7 @@
 
 #include "../../include/cpz.h"
 #include "cpz_kernels.h"
+#include "each_gh.h"
 #include "pair_sum.h"
 #include "rlc.h"
 #include "verify.h"
@@ -873,16 +874,20 @@ inline size_t pad16(size_t x) { return (x + 15) & ~size_t(15); }
 // direct (a small synchronous call, zero_copy()): the kernels read the page-locked block
 // itself through its device view -- no copy on the stream -- and *status_dev / *status_host
 // point at n status bytes after it, which the kernels write the same way.
+constexpr int kStageRowsMax = 7;  // y1 .. s, and the generator rows of cpz_verify_each_gh after them
 struct Staged {
-  Rows rows;  // the first `count` of them
+  Rows rows;  // the first `count` of them (at most five)
+  const void* more[kStageRowsMax - 5] = {};  // rows 5 and 6 of a call that stages more than five
   Ctxs cx;    // offsets relative to the staged blob
 };
 
-int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count, const uint8_t* ctx_bytes,
+int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const* host, int count, const uint8_t* ctx_bytes,
                  const uint64_t* ctx_off, const uint8_t* ctx_present, Staged& out, bool direct = false,
                  uint8_t** status_dev = nullptr, uint8_t** status_host = nullptr, const void* extra = nullptr,
                  size_t extra_bytes = 0, const void** dextra = nullptr) {
-  const void* dev[5] = {};
+  const void* dev[kStageRowsMax] = {};
+  if (count > kStageRowsMax || (count > 5 && extra_bytes))  // in[5] serves row 5 or the extra block
+    return fail(CPZ_EINVAL, "internal: too many staged rows");
   out = Staged{};
   if (status_dev) *status_dev = nullptr;
   if (int rc = check_context_order(ctx_off, n)) return rc;
@@ -923,6 +928,8 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
     }
     for (int k = 0; k < count; k++) dev[k] = d + (size_t)k * n * 32;
     out.rows = Rows(dev[0], dev[1], dev[2], dev[3], dev[4]);
+    out.more[0] = dev[5];
+    out.more[1] = dev[6];
     if (ctx_off)
       out.cx = Ctxs(d + o_ctx, reinterpret_cast<const uint64_t*>(d + o_off), ctx_present ? d + o_pres : nullptr);
     return CPZ_OK;
@@ -934,6 +941,8 @@ int stage_inputs(cpz_ctx* ctx, size_t n, const uint8_t* const host[5], int count
     dev[k] = ctx->in[k].p;
   }
   out.rows = Rows(dev[0], dev[1], dev[2], dev[3], dev[4]);
+  out.more[0] = dev[5];
+  out.more[1] = dev[6];
   if (extra_bytes) {
     CPZ_HIP(ctx->in[5].ensure(extra_bytes));
     CPZ_HIP(hipMemcpyAsync(ctx->in[5].p, extra, extra_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -3757,6 +3766,210 @@ int cpz_verify_each_pairs_many(cpz_ctx* ctx, uint32_t flags, size_t npairs, cons
     }
   }
   return read_back_statuses(ctx, n, status_out);
+}
+
+// ---- a (g, h) pair per entry: cpz_verify_each_gh ----------------------------------------------
+namespace {
+
+// The sponge after Transcript::new() (transcript.rs:29-33), the same for every pair: computed here,
+// so the calls below need no resident set's prefix and leave the generator cache alone.
+cpz::StrobeSnap transcript_new_snap() {
+  cpz::ArrayState st;
+  const cpz::Strobe<cpz::ArrayState> s = cpz::transcript_new(st);
+  cpz::StrobeSnap out{};
+  std::memcpy(out.state, st.b, sizeof(out.state));
+  out.pos = s.pos;
+  out.pos_begin = s.pos_begin;
+  out.flags = s.cur_flags;
+  return out;
+}
+
+// The rows of a call whose entries carry their own generators, on the device, with the challenge
+// buffer (32 bytes per entry of the call) and the statuses.
+struct GhRange {
+  const uint32_t* g = nullptr;
+  const uint32_t* h = nullptr;
+  Rows rows;
+  Ctxs cx;
+  uint32_t* c = nullptr;
+  uint8_t* status = nullptr;
+};
+
+// Entries [a, a + n) of r as the kernels' argument block.
+cpz::GhArgs gh_args(const cpz_ctx* ctx, const GhRange& r, int64_t a, int64_t n, const cpz::StrobeSnap& s0) {
+  cpz::GhArgs ga{};
+  ga.n = n;
+  ga.g = r.g + 8 * a;
+  ga.h = r.h + 8 * a;
+  set_rows(ga, r.rows.at(a));
+  const Ctxs cx = r.cx.at(a);
+  ga.ctx_bytes = cx.bytes;
+  ga.ctx_off = cx.off;
+  ga.ctx_present = cx.present;
+  ga.c = r.c + 8 * a;
+  ga.status = r.status ? r.status + a : nullptr;
+  ga.eq_only = ctx->call_eq ? 1 : 0;
+  ga.s0 = s0;
+  return ga;
+}
+
+// The proofs of one k_verify_quad_gh launch: a proof keeps four tables per quad, twice the
+// eight-lane kernel's two, so a slab holds half of verify_quad_max (8192 on the 256-CU MI355X).
+int64_t gh_chunk_max(const cpz_ctx* ctx) { return verify_quad_max(ctx) / 2; }
+
+// Per-proof verification of the n entries of r in chunks of at most gh_chunk_max(ctx) proofs:
+// k_challenge_gh (stage 0), then k_verify_quad_gh (stage 1), on the chunk's stream.  The chunks
+// alternate over the verify streams and their slabs as launch_quad_pairs_chunks' do and are joined
+// into `st` at the end.  Nothing is read back.
+int launch_gh_chunks(cpz_ctx* ctx, const GhRange& r, int64_t n, hipStream_t st) {
+  static_assert(cpz::kGhProofScratch == 2 * cpz::kQuadProofScratch, "gh_chunk_max: half of verify_quad_max");
+  const int64_t per = gh_chunk_max(ctx);
+  if (per < 1) return fail(CPZ_EINVAL, "internal: no room for the eight-lane kernel's tables");
+  const size_t slab = verify_slab_bytes(ctx);
+  const int64_t chunks = (n + per - 1) / per;
+  const int nst = (int)std::min<int64_t>(CPZ_VERIFY_STREAMS, chunks);
+  const cpz::StrobeSnap s0 = transcript_new_snap();
+  CPZ_HIP(ctx->scratch.ensure((size_t)CPZ_VERIFY_STREAMS * slab));
+  if (nst > 1)
+    if (int rc = fork_verify_streams(ctx, st, nst)) return rc;
+  for (int64_t c = 0; c < chunks; c++) {
+    const int64_t a = c * per;
+    const int k = (int)(c % nst);  // stream k owns scratch slab k
+    hipStream_t sc = k == 0 ? st : ctx->aux_stream[k - 1];
+    cpz::GhArgs ga = gh_args(ctx, r, a, std::min<int64_t>(n - a, per), s0);
+    ga.scratch = static_cast<char*>(ctx->scratch.p) + (size_t)k * slab;
+    ga.max_proofs = per;
+    {
+      StageTimer tc(ctx, 0, sc);
+      CPZ_HIP(cpz::launch_challenge_gh(ga, sc));
+    }
+    StageTimer t(ctx, 1, sc);
+    CPZ_HIP(cpz::launch_verify_quad_gh(ga, sc));
+  }
+  if (nst > 1) return join_verify_streams(ctx, st, nst);
+  return CPZ_OK;
+}
+
+// The argument checks the three calls share, in the bulk call's order and wording.
+int gh_head_checks(cpz_ctx* ctx, size_t n, const void* g, const void* h, const Rows& rows, bool need_s,
+                   const void* out) {
+  if (!ctx) return fail(CPZ_EINVAL, "null context");
+  if (n == 0) return fail(CPZ_EEMPTY, "Cannot verify empty batch");
+  if (n > CPZ_PAIRS_BULK_MAX_PROOFS)
+    return fail_exceeds("n", n, "CPZ_PAIRS_BULK_MAX_PROOFS", CPZ_PAIRS_BULK_MAX_PROOFS);
+  if (!g || !h || !rows.y1 || !rows.y2 || !rows.r1 || !rows.r2 || (need_s && !rows.s) || !out)
+    return fail(CPZ_EINVAL, "null input pointer");
+  return CPZ_OK;
+}
+
+// The host rows of a call on the device, all through stage_inputs (one page-locked block and one
+// copy for a small call): y1, y2, r1, r2, s (null: cpz_challenges_gh has none), then g and h.
+int gh_stage(cpz_ctx* ctx, size_t n, const uint8_t* g, const uint8_t* h, const uint8_t* const rows5[5],
+             const uint8_t* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present, GhRange& r) {
+  // a call without s stages g in its place, so that the rows stay packed
+  const bool has_s = rows5[4] != nullptr;
+  const uint8_t* host[kStageRowsMax] = {rows5[0], rows5[1], rows5[2], rows5[3], has_s ? rows5[4] : g,
+                                        has_s ? g : h, has_s ? h : nullptr};
+  Staged in;
+  if (int rc = stage_inputs(ctx, n, host, has_s ? 7 : 6, ctx_bytes, ctx_off, ctx_present, in)) return rc;
+  r.rows = in.rows;
+  if (has_s) {
+    r.g = static_cast<const uint32_t*>(in.more[0]);
+    r.h = static_cast<const uint32_t*>(in.more[1]);
+  } else {
+    r.g = in.rows.s;
+    r.h = static_cast<const uint32_t*>(in.more[0]);
+    r.rows.s = nullptr;
+  }
+  r.cx = in.cx;
+  return CPZ_OK;
+}
+
+}  // namespace
+
+int cpz_verify_each_gh(cpz_ctx* ctx, uint32_t flags, size_t n, const uint8_t* g, const uint8_t* h, const uint8_t* y1,
+                       const uint8_t* y2, const uint8_t* r1, const uint8_t* r2, const uint8_t* s,
+                       const uint8_t* ctx_bytes, const uint64_t* ctx_off, const uint8_t* ctx_present,
+                       uint8_t* status_out) {
+  int rc = gh_head_checks(ctx, n, g, h, Rows(y1, y2, r1, r2, s), true, status_out);
+  if (rc) return rc;
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  const uint8_t* host[5] = {y1, y2, r1, r2, s};
+  GhRange r;  // stage_inputs checks the offsets' order before it copies anything
+  if ((rc = gh_stage(ctx, n, g, h, host, ctx_bytes, ctx_off, ctx_present, r))) return rc;
+  CPZ_HIP(ctx->st.ensure(n));
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  r.c = static_cast<uint32_t*>(ctx->c.p);
+  r.status = static_cast<uint8_t*>(ctx->st.p);
+  {
+    StageTimer span(ctx, 5, st);
+    if ((rc = launch_gh_chunks(ctx, r, (int64_t)n, st))) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+  }
+  return read_back_statuses(ctx, n, status_out);
+}
+
+int cpz_verify_each_gh_device(cpz_ctx* ctx, uint32_t flags, size_t n, const void* d_g, const void* d_h,
+                              const void* d_y1, const void* d_y2, const void* d_r1, const void* d_r2, const void* d_s,
+                              const void* d_ctx_bytes, const uint64_t* d_ctx_off, const uint8_t* d_ctx_present,
+                              void* d_status_out, void* stream) {
+  const Rows rows(d_y1, d_y2, d_r1, d_r2, d_s);
+  int rc = gh_head_checks(ctx, n, d_g, d_h, rows, true, d_status_out);
+  if (rc) return rc;
+  if (!rows.aligned() || !aligned16(d_g) || !aligned16(d_h))
+    return fail(CPZ_EINVAL, "device inputs must be 16-byte aligned");
+  if ((rc = check_contexts(d_ctx_bytes, d_ctx_off, n, true))) return rc;
+  CallLock lock(ctx, flags);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+  if ((rc = order_after_last(ctx, st))) return rc;
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  GhRange r;
+  r.g = static_cast<const uint32_t*>(d_g);
+  r.h = static_cast<const uint32_t*>(d_h);
+  r.rows = rows;
+  r.cx = Ctxs(d_ctx_bytes, d_ctx_off, d_ctx_off ? d_ctx_present : nullptr);
+  r.c = static_cast<uint32_t*>(ctx->c.p);
+  r.status = static_cast<uint8_t*>(d_status_out);
+  {
+    StageTimer span(ctx, 5, st);
+    rc = launch_gh_chunks(ctx, r, (int64_t)n, st);
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  return record_last(ctx, st);  // not synchronised: later calls on the context are ordered after it
+}
+
+int cpz_challenges_gh(cpz_ctx* ctx, size_t n, const uint8_t* g, const uint8_t* h, const uint8_t* y1, const uint8_t* y2,
+                      const uint8_t* r1, const uint8_t* r2, const uint8_t* ctx_bytes, const uint64_t* ctx_off,
+                      const uint8_t* ctx_present, uint8_t* c_out) {
+  int rc = gh_head_checks(ctx, n, g, h, Rows(y1, y2, r1, r2, nullptr), false, c_out);
+  if (rc) return rc;
+  if ((rc = check_contexts(ctx_bytes, ctx_off, n))) return rc;
+  CallLock lock(ctx);
+  CPZ_HIP(hipSetDevice(ctx->device));
+  if ((rc = order_after_last(ctx, ctx->stream))) return rc;
+  const uint8_t* host[5] = {y1, y2, r1, r2, nullptr};
+  GhRange r;  // no s: no response status either
+  if ((rc = gh_stage(ctx, n, g, h, host, ctx_bytes, ctx_off, ctx_present, r))) return rc;
+  CPZ_HIP(ctx->c.ensure(n * 32));
+  r.c = static_cast<uint32_t*>(ctx->c.p);
+  const cpz::GhArgs ga = gh_args(ctx, r, 0, (int64_t)n, transcript_new_snap());
+  {
+    StageTimer tc(ctx, 0, ctx->stream);
+    CPZ_HIP(cpz::launch_challenge_gh(ga, ctx->stream));
+  }
+  CPZ_HIP(hipMemcpyAsync(c_out, ctx->c.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  CPZ_HIP(hipStreamSynchronize(ctx->stream));
+  return CPZ_OK;
 }
 
 int cpz_challenges(cpz_ctx* ctx, const uint8_t g[32], const uint8_t h[32], size_t n, const uint8_t* y1,

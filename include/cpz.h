@@ -50,6 +50,7 @@ extern "C" {
 #define CPZ_STATUS_BAD_SCALAR 3
 #define CPZ_STATUS_IDENTITY 4
 #define CPZ_STATUS_ZERO_S 5
+#define CPZ_STATUS_BAD_GENERATOR 6 /* cpz_verify_each_gh only: the entry's own (g, h) is no valid pair */
 
 /* ABI revision of this header (cpz_abi_version): bumped whenever an entry point's signature or
  * an array size it writes changes, so that callers built against another header can refuse
@@ -232,6 +233,65 @@ int cpz_verify_each_pairs_many(cpz_ctx *ctx, uint32_t flags, size_t npairs, cons
                                const uint8_t *r1, const uint8_t *r2, const uint8_t *s,
                                const uint8_t *ctx_bytes, const uint64_t *ctx_off,
                                const uint8_t *ctx_present, uint8_t *status_out);
+
+/* Per-proof verification in which every entry carries its own generators: two more rows, g[i] and
+ * h[i] (n x 32 bytes each), instead of a pair list and an index -- the shape of decryption-share
+ * and VRF / OPRF evaluation proofs, where g is a fixed base and h a fresh point per proof (a
+ * ciphertext component, a hashed input: cpz_hash_to_group_device can leave 2^20 of them in device
+ * memory).  n may be up to CPZ_PAIRS_BULK_MAX_PROOFS; the number of distinct pairs has no bound.
+ * Rows may repeat, and a row may be the default pair.
+ *   status_out[i] is CPZ_STATUS_BAD_GENERATOR if Parameters::with_generators(g_i, h_i) would fail
+ * (gadgets.rs:77-103): g_i or h_i does not decode, is the identity (32 zero bytes), or g_i == h_i
+ * (encodings are canonical, so the bytes decide).  Status 6 wins over every other status -- in
+ * the reference no entry exists under such parameters -- and is never a call-level error: these
+ * calls do not return CPZ_EGENERATOR.  Otherwise status_out[i] is exactly what cpz_verify_each_ex
+ * reports for entry i under (g_i, h_i): every status 0-5, with CPZ_CALL_EQUATIONS_ONLY, the
+ * context's commitment-check mode and every context shape.
+ *   The pair is used once, so nothing is built per pair and nothing is kept: every entry takes
+ * the byte-wise transcript from the one snapshot no pair enters (stage 0), and the eight-lane
+ * kernel decodes the entry's generator beside its Y and R and builds the small tables of B and
+ * 2^128 B (cpz_verify_each_pairs_many's, 128 doublings per generator) in the proof's own scratch
+ * (stages 1 / 5).  A proof keeps four tables per equation, so a launch holds half the eight-lane
+ * bound: the chunk bound is half of it, 8192 proofs on the 256-CU MI355X (7040 on a 110-CU part);
+ * the chunks alternate over the verify streams.  No cache is touched: neither the generator
+ * cache nor the light-set cache nor its least-recently-used order (cpz_ctx_pairs_resident answers
+ * the same before and after); no comb is built, no stage 7 or stage 13 is recorded, and
+ * cpz_ctx_fallback_stats is left alone.
+ *   Measured on MI355X (profiles/each_gh_ab.json, host buffers, medians, against
+ * cpz_verify_each_pairs_many over consecutive slices of 4096 entries, a distinct pair per entry):
+ * n = 1000: 0.69 ms (0.68 - 0.70) against 0.82 (0.81 - 0.85), one call on each side; n = 4096: 0.75
+ * (0.74 - 0.78) against 0.95 (0.94 - 1.01), one call on each side; n = 2^17: 10.4 ms (10.3 - 10.7)
+ * against 30.4 (29.8 - 30.8) for the 32 calls; n = 2^20: 77.5 ms (77.3 - 77.7) against 243.5 (241.5 -
+ * 244.8) for the 256 calls, the verify launches taking 72.0 ms of GPU time (14.6 M proofs/s); every
+ * pair of ranges apart.  When not to use it: where many entries share few pairs
+ * cpz_verify_each_pairs_many builds a pair's tables once per call instead of once per proof -- 2^17
+ * entries over 16 pairs take 9.74 ms (9.73 - 9.77) here against 6.78 (6.77 - 6.84) in one such call,
+ * 1.44x the time.
+ * Checked before anything is launched or written, in the bulk call's wording: n == 0 ->
+ * CPZ_EEMPTY; a null pointer, n > CPZ_PAIRS_BULK_MAX_PROOFS, bad context offsets (host form) or
+ * a device row that is not 16-byte aligned (device form) -> CPZ_EINVAL.
+ *   cpz_verify_each_gh         host buffers; returns synchronised.
+ *   cpz_verify_each_gh_device  device-resident rows; enqueues on `stream` (NULL: the context's
+ *                              own) and does not synchronise: like cpz_verify_each_device, later
+ *                              calls on the context are ordered after it, and the statuses are
+ *                              the caller's to read after the stream's own synchronisation.  No
+ *                              part of the call reads anything back to the host.
+ *   cpz_challenges_gh          the entries' Fiat-Shamir challenges alone (32 bytes each), host
+ *                              buffers; returns synchronised. */
+int cpz_verify_each_gh(cpz_ctx *ctx, uint32_t flags, size_t n,
+                       const uint8_t *g, const uint8_t *h,
+                       const uint8_t *y1, const uint8_t *y2, const uint8_t *r1, const uint8_t *r2,
+                       const uint8_t *s, const uint8_t *ctx_bytes, const uint64_t *ctx_off,
+                       const uint8_t *ctx_present, uint8_t *status_out);
+int cpz_verify_each_gh_device(cpz_ctx *ctx, uint32_t flags, size_t n,
+                              const void *d_g, const void *d_h,
+                              const void *d_y1, const void *d_y2, const void *d_r1, const void *d_r2,
+                              const void *d_s, const void *d_ctx_bytes, const uint64_t *d_ctx_off,
+                              const uint8_t *d_ctx_present, void *d_status_out, void *stream);
+int cpz_challenges_gh(cpz_ctx *ctx, size_t n, const uint8_t *g, const uint8_t *h,
+                      const uint8_t *y1, const uint8_t *y2, const uint8_t *r1, const uint8_t *r2,
+                      const uint8_t *ctx_bytes, const uint64_t *ctx_off, const uint8_t *ctx_present,
+                      uint8_t *c_out);
 
 /* The light-set cache behind the mixed-pair calls (cpz_verify_each_pairs*, cpz_prove_pairs*, the
  * fallback of cpz_verify_batch_pairs): a context keeps the 128-entry tables and transcript

@@ -22,6 +22,7 @@ pub const CPZ_STATUS_BAD_POINT: u8 = 2;
 pub const CPZ_STATUS_BAD_SCALAR: u8 = 3;
 pub const CPZ_STATUS_IDENTITY: u8 = 4;
 pub const CPZ_STATUS_ZERO_S: u8 = 5;
+pub const CPZ_STATUS_BAD_GENERATOR: u8 = 6;
 
 pub const CPZ_PARSE_OK: u8 = 0;
 pub const CPZ_PARSE_TOO_SMALL: u8 = 1;
@@ -110,6 +111,17 @@ extern "C" {
                                       pair_idx: *const u32, y1: *const u8, y2: *const u8, r1: *const u8,
                                       r2: *const u8, s: *const u8, ctx_bytes: *const u8, ctx_off: *const u64,
                                       ctx_present: *const u8, status_out: *mut u8) -> c_int;
+    pub fn cpz_verify_each_gh(ctx: *mut cpz_ctx, flags: u32, n: usize, g: *const u8, h: *const u8, y1: *const u8,
+                              y2: *const u8, r1: *const u8, r2: *const u8, s: *const u8, ctx_bytes: *const u8,
+                              ctx_off: *const u64, ctx_present: *const u8, status_out: *mut u8) -> c_int;
+    pub fn cpz_verify_each_gh_device(ctx: *mut cpz_ctx, flags: u32, n: usize, d_g: *const c_void, d_h: *const c_void,
+                                     d_y1: *const c_void, d_y2: *const c_void, d_r1: *const c_void,
+                                     d_r2: *const c_void, d_s: *const c_void, d_ctx_bytes: *const c_void,
+                                     d_ctx_off: *const u64, d_ctx_present: *const u8, d_status_out: *mut c_void,
+                                     stream: *mut c_void) -> c_int;
+    pub fn cpz_challenges_gh(ctx: *mut cpz_ctx, n: usize, g: *const u8, h: *const u8, y1: *const u8, y2: *const u8,
+                             r1: *const u8, r2: *const u8, ctx_bytes: *const u8, ctx_off: *const u64,
+                             ctx_present: *const u8, c_out: *mut u8) -> c_int;
     pub fn cpz_verify_each_pairs_device(ctx: *mut cpz_ctx, flags: u32, npairs: usize, pairs: *const u8, n: usize,
                                         d_pair_idx: *const u32, d_y1: *const c_void, d_y2: *const c_void,
                                         d_r1: *const c_void, d_r2: *const c_void, d_s: *const c_void,
